@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: reads/s classified on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path (2-bit pack -> minimizer sketch -> index probe ->
@@ -13,9 +13,16 @@ across ranks with no other collective ("weak" scaling: every rank classifies its
 `--reads` reads per step).
 
 Workload at N=1 = BASELINE.json configs[1]: 100 k synthetic 5 kb reads vs the 20-genome
-index.  Rank 0 prints one JSON line with `roofline` (index-probe kernel, HIP-event timed on
-the engine stream over the timed region) and, at N=1, `cpu_baseline` (the CPU oracle timed on
-a bounded sample of the same reads on the host cores).
+index.  A plain run sets up, warms up, times the `--steps` steps and prints one JSON line on
+rank 0: the headline figure, `ms_per_step`, and what the timed steps themselves yield (stage
+times, counters, `roofline_probe` / `roofline_stage` from the HIP events of the timed region).
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy.
+
+`--full` adds, at N=1, the legs that take runs of their own: `chain_level` (the same batch
+without base-level alignment), `roofline` of the dominant alignment kernel (the alignment
+kernels one at a time), `cpu_baseline` (the CPU oracle timed on a bounded sample of the same
+reads on the host cores) and `end_to_end` (PCIe-inclusive rates).  Without it those keys are
+null and `roofline` is the probe kernel's.
 """
 import argparse
 import json
@@ -45,7 +52,15 @@ def parse():
     ap.add_argument("--min-len", type=int, default=2_000_000)
     ap.add_argument("--max-len", type=int, default=7_000_000)
     ap.add_argument("--min-mapq", type=int, default=60)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="reads for the CPU baseline (-1 auto, 0 off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs of --mode batch at one GPU, each a run of its own after the timed steps: "
+                         "chain_level, the alignment kernels one at a time (roofline of the dominant kernel), cpu_baseline, "
+                         "end_to_end.  Off by default: a plain run measures the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64; rank 0's arrays; at most 64 MB in all -- a fixed, seeded sample of the rows of larger "
+                         "outputs).  The inputs are seeded: the same arguments give the same inputs in every run")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="reads for the CPU baseline of --full (-1 auto, 0 off)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default): every rank classifies --reads reads per step; strong: --total-reads reads per "
                          "step are split over the ranks (BASELINE config 3 is 10 M reads over 8 GPUs)")
@@ -76,7 +91,29 @@ def parse():
     ap.add_argument("--stream-rate", type=int, default=400)
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "probe_traffic.json"),
                     help="optional PMC-derived HBM bytes per launch of the probe kernel")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: ms_per_step is the time of one timed step")
+    if args.dump_outputs and args.mode in ("stream", "files"):
+        ap.error("--dump-outputs goes with --mode batch, shard or config3")
+    return args
+
+
+DUMP_BYTES = 60_000_000        # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> integer array, one row per read or per taxon) as `path`/<name>.npy in float64,
+    exact for every value the kernels write (int32, and counts far below 2^53).  Above DUMP_BYTES in all, every array
+    keeps the same fraction of its rows, drawn once with a fixed seed and kept in order: two runs with the same
+    arguments write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 8
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0x6D6E63).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def launch_ranks(n):
@@ -263,11 +300,14 @@ def main():
     counters = engine.counters()
     assign = d_assign.cpu().numpy()
     counts = d_counts.cpu().numpy().reshape(-1, 3)
+    dumped = None
+    if args.dump_outputs and rank == 0:          # what classify_device handed back in the last timed step (the legs below reuse the buffers)
+        dumped = {"assign": assign, "best": d_best.cpu().numpy().reshape(-1, 4), "nhits": d_nhits.cpu().numpy(), "counts": counts}
 
     # the same batch without base-level alignment (a secondary figure: the path of north_star's
     # kernel list; its NM / mlen / mapq are chain-level estimates, not what monica reads from mappy)
     chain_level = None
-    if args.contract == "dp" and world == 1:
+    if args.full and args.contract == "dp" and world == 1:
         engine.set_contract(_capi.CONTRACT_CHAIN)
         for _ in range(2):
             step()
@@ -286,7 +326,7 @@ def main():
     # the alignment kernels one at a time (they share the chip in the timed steps): HIP events around
     # each launch, on the stream it runs on -- the dominant kernel's own duration for `roofline`
     dp_kernel_ms = None
-    if args.contract == "dp" and world == 1:
+    if args.full and args.contract == "dp" and world == 1:
         base_debug = env_debug
         engine.set_debug(base_debug | 0x10000)
         engine.set_profiling(True)
@@ -304,6 +344,8 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
 
     # ---------------------------------------------------------------- roofline of the dominant kernel
     # With base-level alignment the batch is bound by the gap-filling kernel mnc_dp_fillp<16> (32-cell
@@ -427,7 +469,7 @@ def main():
 
     # ---------------------------------------------------------------- CPU baseline (oracle, bounded sample)
     cpu = None
-    if world == 1 and args.cpu_sample != 0:
+    if args.full and world == 1 and args.cpu_sample != 0:
         from oracle import pyoracle
         cores = os.cpu_count() or 1
         try:
@@ -465,7 +507,7 @@ def main():
     # the PCIe-inclusive rate (never `value`): fresh batches from page-locked host memory through the
     # host-buffer entry point -- H2D of the bases, all kernels, D2H of the decisions
     end_to_end = None
-    if world == 1:
+    if args.full and world == 1:
         import threading
         hb = _capi.pinned_array(bases)
         engine.classify(hb, offsets, args.min_mapq)
@@ -693,6 +735,8 @@ def shard_mode(args, names, seqs, rank, local_rank, world, dev):
     assign = result["assign"].cpu().numpy()
     ranks = rank_report(world, args.backend, done[0], dev)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"assign": assign})        # the merged decisions, the same on every rank
         ok = truth >= 0
         print(json.dumps({
             "metric": "reads/sec classified, index sharded (BASELINE config 4)", "value": round(n * args.steps / elapsed, 1),
@@ -786,6 +830,8 @@ def config3_mode(args, names, seqs, rank, local_rank, world, dev):
         dist.all_reduce(local)
     ranks = rank_report(world, args.backend, done[0], dev)
     if rank == 0:
+        if args.dump_outputs:                                  # rank 0's share of the reads; the count table of the whole job
+            dump_outputs(args.dump_outputs, {"assign": assign, "best": d_best.cpu().numpy().reshape(-1, 4), "counts": counts})
         mp, ok, bad = (int(x) for x in local.cpu())
         print(json.dumps({
             "metric": "reads/sec classified, 10 M-read job (BASELINE config 3)", "value": round(total * args.steps / elapsed, 1),

@@ -68,7 +68,7 @@ def test_gpus_2_alone_reports_two_ranks():
 
 @pytest.mark.gpu
 def test_one_rank_line_carries_the_timed_region_and_both_cpu_baselines():
-    r = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "4000", "--cpu-sample", "300")
+    r = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "4000", "--cpu-sample", "300", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["rccl_ranks"] is None and out["ranks"]["reads_per_rank"] == [8000]
@@ -104,3 +104,56 @@ def test_four_ranks_rehearse_the_sharded_modes_on_one_device():
     assert out["n_gpus"] == 4 and out["group_ranks"] == 4
     assert out["ranks"]["reads_per_rank"] == [5001, 5000, 5000, 5000]      # dist.shard_bounds: the first rank takes the odd read
     assert out["counts_equal_mapped_reads"] and out["mapped_reads"] > 0.9 * 20001 and out["random_reads_mapped"] == 0
+
+
+def test_dump_outputs_is_float64_exact_and_sampled_the_same_way_every_time(tmp_path):
+    """`--dump-outputs`: small outputs are written whole and exactly; outputs above the size limit keep the same seeded
+    rows of every array in every run, in order, and stay under 64 MB in all."""
+    import importlib.util
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assign = np.arange(-3, 997, dtype=np.int32)
+    counts = np.array([[2**40 + 1, 2, 3], [4, 5, 6]], dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "small"), {"assign": assign, "counts": counts})
+    got = np.load(tmp_path / "small" / "assign.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, assign)
+    assert np.array_equal(np.load(tmp_path / "small" / "counts.npy").astype(np.int64), counts)
+    n = 3_000_000                                                       # 3 M x (1 + 4) x 8 B = 120 MB as float64
+    big = {"assign": np.arange(n, dtype=np.int32), "best": np.arange(4 * n, dtype=np.int32).reshape(n, 4)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a, b = np.load(tmp_path / "a" / "assign.npy"), np.load(tmp_path / "a" / "best.npy")
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000
+    assert 0.4 * n < len(a) < n and (np.diff(a) > 0).all()               # a real sample, rows in their order
+    assert np.array_equal(b[:, 0], 4 * a) and b.shape == (len(a), 4)     # the same rows of both arrays
+    assert np.array_equal(a, np.load(tmp_path / "b" / "assign.npy")) and np.array_equal(b, np.load(tmp_path / "b" / "best.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_only_and_dumps_what_the_last_step_returned(tmp_path):
+    """Without --full the line holds the headline figure and no leg with runs of its own; --dump-outputs writes the arrays
+    classify_device handed back in the last timed step, and they agree with the line's own summary of them."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    r = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "2000", "--genomes", "4", "--min-len", "200000",
+                  "--max-len", "300000", "--dump-outputs", str(out_dir), timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 2 and out["ranks"]["reads_per_rank"] == [4000]
+    assert abs(out["timed_region_s"] * 1e3 / 2 - out["ms_per_step"]) < 0.06
+    assert abs(out["value"] - 4000 / out["timed_region_s"]) / out["value"] < 2e-2
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in out
+    for k in ("cpu_baseline", "chain_level", "end_to_end"):
+        assert out[k] is None, k
+    assert "kernels_one_at_a_time_ms" not in out["roofline"]
+    got = {f[:-4]: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+    assert sorted(got) == ["assign", "best", "counts", "nhits"] and all(a.dtype == np.float64 for a in got.values())
+    assert got["assign"].shape == (2000,) and got["best"].shape == (2000, 4) and got["nhits"].shape == (2000,)
+    assert got["counts"].shape == (4, 3)
+    assert int((got["assign"] >= 0).sum()) == out["mapped_reads_last_step"] > 1000
+    assert int(got["counts"][:, 0].sum()) == out["counts_checksum"]
+    assert (got["nhits"][got["assign"] >= 0] >= 1).all()

@@ -9,7 +9,7 @@ for lib in "" "$other" "" "$other"; do
   echo "== ${lib:-library of the tree}" >> $out
   export MONICA_AMD_LIB=$lib
   [ -z "$lib" ] && unset MONICA_AMD_LIB
-  python bench.py --steps 10 --warmup 3 --cpu-sample 0 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("bench", d["value"], d["ms_per_step"], d["stage_ms_per_step"]["dp_fill"], d["roofline"]["kernels_one_at_a_time_ms"])' >> $out
+  python bench.py --steps 10 --warmup 3 --cpu-sample 0 --full 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("bench", d["value"], d["ms_per_step"], d["stage_ms_per_step"]["dp_fill"], d["roofline"]["kernels_one_at_a_time_ms"])' >> $out
   python tools/small_batches.py 3000,12500,30000 2>/dev/null | cut -c1-70 >> $out
   python tools/err_profile.py 500 400 400 30000 2>/dev/null | head -1 >> $out
   python tools/err_profile.py 700 450 450 30000 2>/dev/null | head -1 >> $out
