@@ -131,6 +131,17 @@ int  mnc_engine_create(mnc_index *idx, int device, mnc_engine **out);
 #define MNC_CONTRACT_DP    0
 #define MNC_CONTRACT_CHAIN 1
 int  mnc_engine_set_contract(mnc_engine *eng, int contract);
+/* Reads of 2^20 bases or more, which index.map() takes like any other (aligner.py:193, 215).  off (0, the default): such a
+ * read comes back MNC_SKIPPED.  on (1): reads of up to MNC_MAX_READ_LEN_WIDE bases are classified.  In mnc_classify_batch
+ * the reads below 2^20 bases take the usual pass, untouched by the others; the long ones take one more pass with
+ * 24-bit query positions in the probe's records (an internal batch of those reads alone; at most MNC_MAX_READS_WIDE of
+ * them per call), and the results are put back by read ordinal: out_assign / out_best / out_nhits, mnc_engine_fetch_hits
+ * (one CSR over all reads, in read order) and mnc_engine_get_counters (sums of both passes) cover the whole call.  The
+ * stage dumps (mnc_engine_dump) and timings after such a mixed call describe the wide pass -- the long reads, in their
+ * order -- only; after a call whose reads are all long they describe the call in full. */
+#define MNC_MAX_READ_LEN_WIDE ((1 << 24) - 1)
+#define MNC_MAX_READS_WIDE    (1 << 16)
+int  mnc_engine_set_long_reads(mnc_engine *eng, int on);
 void mnc_engine_destroy(mnc_engine *eng);
 /* another index part behind the same engine: `index = index_loader(part)` in the reference's loop over the
  * parts of a database (aligner.py:91-103).  Same k / w / match score as the index the engine was made for. */
@@ -143,8 +154,13 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   k = 15, w = 10 only                          mnc_index_build*: MNC_ERR_UNSUPPORTED (the one setting monica uses,
  *                                                aligner.py:45: preset 'map-ont')
  *   a read of 2^20 bases or more                 mnc_classify_batch: that read alone comes back MNC_SKIPPED (no hits); the
- *                                                other reads of the batch are classified as ever.  mnc_classify_device
+ *   (default)                                    other reads of the batch are classified as ever.  mnc_classify_device
  *                                                (device-resident batches; the caller states max_read_len): MNC_ERR_UNSUPPORTED
+ *   ... after mnc_engine_set_long_reads(eng, 1)  classified like any other read, up to MNC_MAX_READ_LEN_WIDE bases (exact; a
+ *                                                second pass over those reads with wide probe records).  A longer read
+ *                                                alone comes back MNC_SKIPPED; mnc_classify_device runs the whole call wide
+ *                                                when max_read_len >= 2^20, with at most MNC_MAX_READS_WIDE reads, and
+ *                                                answers MNC_ERR_UNSUPPORTED beyond either bound
  *   one kernel call of a read's alignment whose  that read alone comes back MNC_SKIPPED.  (tlen x qlen <= 1e8 with more
  *   direction matrix exceeds 256 MB              than 256 MB of direction bytes: a few hundred query bases against > 300 000
  *                                                target bases -- mm_align1 makes no such call with max_gap = 5 000)

@@ -43,6 +43,9 @@ SEG_DTYPE = np.dtype([(k, np.int32) for k in ("read", "reg", "kind", "rid", "rev
                                               "ai", "big", "n_cigar", "zdropped", "zdrop_code", "max", "max_t", "max_q", "score",
                                               "reach_end", "mqe_t", "pad")] + [("cig_off", np.int64)])
 CONTRACT_DP, CONTRACT_CHAIN = 0, 1
+MAX_READ_LEN = (1 << 20) - 1            # the longest read the usual pass classifies
+MAX_READ_LEN_WIDE = (1 << 24) - 1       # MNC_MAX_READ_LEN_WIDE: ... and the pass for long reads (Engine.set_long_reads)
+MAX_READS_WIDE = 1 << 16                # MNC_MAX_READS_WIDE
 
 # every symbol include/monica_amd.h declares (checked by tests/test_capi.py)
 EXPORTS = [
@@ -53,7 +56,7 @@ EXPORTS = [
     "mnc_engine_create", "mnc_engine_destroy", "mnc_engine_stream", "mnc_engine_device_bytes", "mnc_index_device_bytes", "mnc_engine_set_index",
     "mnc_classify_batch", "mnc_engine_prefetch", "mnc_engine_prefetch_cancel", "mnc_classify_device", "mnc_engine_sync", "mnc_engine_fetch_hits",
     "mnc_counts", "mnc_best_hit",
-    "mnc_engine_set_profiling", "mnc_engine_set_debug", "mnc_engine_set_contract", "mnc_index_set_host_tables", "mnc_index_set_region_bits", "mnc_engine_dump_tables",
+    "mnc_engine_set_profiling", "mnc_engine_set_debug", "mnc_engine_set_contract", "mnc_engine_set_long_reads", "mnc_index_set_host_tables", "mnc_index_set_region_bits", "mnc_engine_dump_tables",
     "mnc_comm_unique_id", "mnc_comm_init_rank", "mnc_comm_destroy", "mnc_comm_count", "mnc_allreduce_counts", "mnc_allgather_summaries", "mnc_shard_summary", "mnc_merge_summaries", "mnc_engine_get_timings", "mnc_stage_name", "mnc_stage_kernel",
     "mnc_engine_get_counters", "mnc_engine_dump",
     "mnc_fastq_open", "mnc_fastq_close", "mnc_fastq_next", "mnc_fastq_detach_batch", "mnc_fastq_remaining", "mnc_fastq_bases", "mnc_fastq_offsets",
@@ -146,6 +149,7 @@ def lib():
     sig("mnc_index_set_region_bits", i32, [vp, i32])
     sig("mnc_engine_dump_tables", i32, [vp, vp, C.c_int64, vp])
     sig("mnc_engine_set_contract", i32, [vp, i32])
+    sig("mnc_engine_set_long_reads", i32, [vp, i32])
     sig("mnc_comm_unique_id", i32, [vp])
     sig("mnc_comm_init_rank", i32, [vp, i32, i32, C.POINTER(vp)])
     sig("mnc_comm_destroy", i32, [vp])
@@ -473,6 +477,11 @@ class Engine:
     def set_contract(self, contract):
         """CONTRACT_DP (default): base-level alignment as mappy runs it; CONTRACT_CHAIN: stop after chaining."""
         check(lib().mnc_engine_set_contract(self._h, int(contract)))
+
+    def set_long_reads(self, on=True):
+        """Reads of 2^20 .. MAX_READ_LEN_WIDE bases are classified (a second, wide pass over them) instead of coming
+        back SKIPPED.  Off by default."""
+        check(lib().mnc_engine_set_long_reads(self._h, 1 if on else 0))
 
     def cigars(self):
         """CIGARs [(len, op), ...] of the regions of the last batch, in DUMP_REGS order."""

@@ -302,8 +302,9 @@ def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_qua
         _trace("classify", batch.n, t1)
         n_skipped = int((out[0] == _capi.SKIPPED).sum())
         if n_skipped:
-            # index.map() takes a read of any length (aligner.py:193, 215); the kernels stop at 2^20 bases.  Such a read
-            # costs neither its sample nor its batch: it has no hits (-> unmapped/), and the run says so
+            # index.map() takes a read of any length (aligner.py:193, 215); the kernels stop at 2^20 bases (at 2^24 with
+            # MONICA_AMD_LONG_READS=1: then fewer reads are counted here).  Such a read costs neither its sample nor its
+            # batch: it has no hits (-> unmapped/), and the run says so
             print(f"{sample_name}: {n_skipped} read(s) beyond the device limits (2^20 bases or more) not classified -> unmapped")
         return out
 

@@ -39,6 +39,20 @@ constexpr uint32_t HIT_HIGH = 0x7fffffffu;  // cnt marker: occurrences >= mid_oc
 
 // 64-bit query record: [21:0] rest of the hash, [22] strand, [23] tandem,
 // [43:24] query position (last base of the k-mer), [63:44] read ordinal in the batch
+//
+// The probe kernels (k_probe.hip) are templates over QB, the bits of a query position.  Field budget of the two forms:
+//                                   QB = QPOS_BITS (20)            QB = QPOS_BITS_WIDE (24)
+//   query record (64 bits)          24 + 20 qpos + 20 ordinal      24 + 24 qpos + 16 ordinal
+//   HitRec.qinfo in bhits (32)      21 qpos|strand + 11 read of    25 qpos|strand + 7 read of the
+//                                   the super-tile (256 used)      super-tile (128: ps_tiles halved)
+//   reads per call                  2^20                           2^16
+//   longest read                    2^20 - 1                       2^24 - 1
+// The wide form serves the pass for reads of 2^20 bases or more (mnc_engine_set_long_reads); HitRec.qinfo in `hits`
+// (after the collect kernel has taken the read bits off), the minimizers and everything from the anchors on hold a
+// position in 31 bits or more in both forms.
+constexpr int QPOS_BITS = 20, QPOS_BITS_WIDE = 24;
+constexpr int WIDE_MAX_READS = 1 << (64 - 24 - QPOS_BITS_WIDE);
+static_assert((PS_TILES_MIN / 2) * PT_READS <= 1 << (31 - QPOS_BITS_WIDE), "the wide super-tile's reads must fit qinfo's spare bits");
 constexpr int PD_MAX_BITS = 14;                             // at most 16384 displacement buckets (16 KiB of LDS)
 // The region comes from the LOW hash bits: minimizers are window minima, so their hash values
 // crowd towards zero and the high bits are far from uniform (region 0 would hold 5x its share).
@@ -250,6 +264,7 @@ struct Batch {
 	                                              // lengths dp_ctr[32 + i], queues dp_ctr[40 + i]
 	int32_t *reg_cnt;             // per read: regions in the skeleton's array (kept + split tails)
 	int slot_pad;                 // region slots per read beyond anchors / 3 (split tails, inversion regions): see reg_slot()
+	int qpos_bits;                // QPOS_BITS_WIDE: the probe kernels' wide records (reads of 2^20 bases or more); anything else: QPOS_BITS
 };
 
 // size classes of the row chaining kernel (anchors per LDS tile)

@@ -445,6 +445,13 @@ struct mnc_engine {
 	int slot_pad = 2;                        // region slots per read beyond anchors / 3 (device.h: reg_slot); grown when a batch runs out
 	Buf inv_ws;                              // mnc_dp_inv: two columns per workgroup
 	int cur_max_read_len = 0;                // of the batch being classified (sizes the stitch kernel's LDS)
+	// reads of 2^20 bases or more (mnc_engine_set_long_reads)
+	int long_reads = 0;                      // the switch
+	bool cur_wide = false;                   // the call being classified runs with the wide probe records (device.h: QPOS_BITS_WIDE)
+	bool have_merged = false;                // the last mnc_classify_batch made two passes: gated hits and counters of the whole call are these
+	std::vector<int64_t> merged_off;
+	std::vector<mnc_hit_t> merged_hits;
+	int64_t merged_ctr[24]{};                // the first pass' counters (added to the wide pass' own)
 	int debug = 0;                           // bit mask (tests): 2 stress build of the chaining ring, 4 displacement bytes read from HBM, 0x10000 alignment kernels one at a time (with stage timers), 0x200000 the stitch kernel reads bases in place (its form for regions beyond its LDS)
 	// last batch
 	Batch B{};
@@ -585,6 +592,25 @@ extern "C" void mnc_engine_destroy(mnc_engine *e)
 	delete e;
 }
 
+// host libm's logf(i) and logf((float)i / a) for i < n, the two look-ups of the MAPQ formula (A.7; indexed by a chain
+// score and by dp_max): 2^21 entries when an engine is made -- beyond any score of a read below 2^20 bases at a = 2 -- and
+// as many as the longest read of a wide call can score (a per base) once long reads are switched on.  The engine's
+// stream must be idle.
+static int logf_tables(mnc_engine *e, int n)
+{
+	if (n <= e->logf_n) return MNC_OK;
+	std::vector<float> lg, lga;
+	try { lg.resize((size_t)n), lga.resize((size_t)n); } catch (const std::bad_alloc &) { set_error("out of host memory (MAPQ look-ups)"); return MNC_ERR_NOMEM; }
+	for (int i = 0; i < n; ++i) lg[i] = logf((float)i), lga[i] = logf((float)i / e->idx->par.a);
+	int rc = e->logf_lut.ensure((size_t)n * 4);
+	if (!rc) rc = e->logf_a_lut.ensure((size_t)n * 4);
+	if (rc) { e->logf_n = 0; return rc; }
+	HIP_TRY(hipMemcpy(e->logf_lut.p, lg.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(e->logf_a_lut.p, lga.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+	e->logf_n = n;
+	return MNC_OK;
+}
+
 extern "C" int mnc_engine_create(mnc_index *idx, int device, mnc_engine **out)
 {
 	if (!idx || !out) return MNC_ERR_ARG;
@@ -634,15 +660,8 @@ extern "C" int mnc_engine_create(mnc_index *idx, int device, mnc_engine **out)
 		for (uint32_t v = (uint32_t)dd; v >>= 1;) ++lg;
 		gap[dd] = (int)(dd * .01 * avg_span) + (dd ? lg >> 1 : 0);
 	}
-	e->logf_n = 1 << 21;
-	std::vector<float> lg((size_t)e->logf_n);
-	for (int i = 0; i < e->logf_n; ++i) lg[i] = logf((float)i);
-	// logf((float)dp_max / a) of the DP branch of the MAPQ formula (A.7), indexed by dp_max
-	std::vector<float> lga((size_t)e->logf_n);
-	for (int i = 0; i < e->logf_n; ++i) lga[i] = logf((float)i / idx->par.a);
 	rc = e->gap_lut.ensure(GAP_LUT * 4);
-	if (!rc) rc = e->logf_lut.ensure((size_t)e->logf_n * 4);
-	if (!rc) rc = e->logf_a_lut.ensure((size_t)e->logf_n * 4);
+	if (!rc) rc = logf_tables(e, 1 << 21);
 	if (!rc) rc = e->dp_ctr.ensure(64 * 8);
 	if (!rc) rc = dp_align_prepare(DP_LDS_BYTES);
 	if (!rc) rc = e->stats.ensure(16 * 8);
@@ -655,8 +674,6 @@ extern "C" int mnc_engine_create(mnc_index *idx, int device, mnc_engine **out)
 	if (!rc) rc = dp_plan_prepare();
 	if (!rc) {
 		he = hipMemcpy(e->gap_lut.p, gap.data(), GAP_LUT * 4, hipMemcpyHostToDevice);
-		if (he == hipSuccess) he = hipMemcpy(e->logf_lut.p, lg.data(), (size_t)e->logf_n * 4, hipMemcpyHostToDevice);
-		if (he == hipSuccess) he = hipMemcpy(e->logf_a_lut.p, lga.data(), (size_t)e->logf_n * 4, hipMemcpyHostToDevice);
 		if (he == hipSuccess) he = hipMemset(e->stats.p, 0, 16 * 8);
 		if (he != hipSuccess) { set_error("table upload failed: %s", hipGetErrorString(he)); rc = MNC_ERR_HIP; }
 	}
@@ -767,6 +784,13 @@ extern "C" int mnc_engine_set_contract(mnc_engine *e, int contract)
 {
 	if (!e || (contract != MNC_CONTRACT_DP && contract != MNC_CONTRACT_CHAIN)) return MNC_ERR_ARG;
 	e->contract = contract;
+	return MNC_OK;
+}
+
+extern "C" int mnc_engine_set_long_reads(mnc_engine *e, int on)
+{
+	if (!e) return MNC_ERR_ARG;
+	e->long_reads = on != 0;
 	return MNC_OK;
 }
 
@@ -904,7 +928,8 @@ static int classify_once(mnc_engine *e, const uint8_t *d_bases, const int64_t *d
 	*overflowed = 0;                                  // 1: query records, 2: segments / CIGAR pools of the alignment stage
 	const size_t nr = (size_t)n_reads, nb = (size_t)total_bases;
 	const int pb_bits = e->didx->pb_bits;
-	const size_t PB_N = (size_t)1 << pb_bits, PS_TILES = (size_t)PS_TILES_MIN;
+	// (the wide records leave seven bits for a read of its super-tile: device.h)
+	const size_t PB_N = (size_t)1 << pb_bits, PS_TILES = (size_t)(e->cur_wide ? PS_TILES_MIN / 2 : PS_TILES_MIN);
 	const size_t n_tiles = (nr + PT_READS - 1) / PT_READS, n_super = (n_tiles + PS_TILES - 1) / PS_TILES;
 	// query records: a (w,k)-minimizer sketch keeps ~2/(w+1) of the k-mers; room for a third
 	// of the bases, and the whole batch is redone with room for all of them if that overflows
@@ -945,10 +970,12 @@ static int classify_once(mnc_engine *e, const uint8_t *d_bases, const int64_t *d
 	B.table = e->didx->table, B.filter = e->didx->filter, B.disp = e->didx->disp, B.salt = e->didx->salt, B.disp_in_lds = (e->didx->disp_bits <= PD_MAX_BITS && !(e->debug & 4)) ? 1 : 0, B.positions = e->didx->positions;
 	B.region_bits = e->didx->region_bits, B.disp_bits = e->didx->disp_bits;
 	B.pb_bits = pb_bits, B.pb_n = (uint32_t)PB_N, B.ps_tiles = (uint32_t)PS_TILES;
+	B.qpos_bits = e->cur_wide ? QPOS_BITS_WIDE : QPOS_BITS;
 	B.contig_genome = e->didx->contig_genome, B.mid_occ = idx->mid_occ, B.n_genomes = (int)idx->genome_name.size();
 	{
 		// an anchor is (strand, contig, position, tandem flag, query position < 2^20): when that
-		// fits 64 bits the sort works on packed words (k_sort.hip)
+		// fits 64 bits the sort works on packed words (k_sort.hip) -- in the LDS size classes, which a read of
+		// 65 536 bases or more never enters (mnc_bin_reads), so the wide pass needs no other word
 		int64_t longest = 1;
 		for (int64_t l : idx->contig_len) longest = std::max(longest, l);
 		int rb = 1, pb = 1;
@@ -1261,11 +1288,23 @@ extern "C" int mnc_classify_device(mnc_engine *e, const uint8_t *d_bases, const 
 {
 	if (!e || !d_offsets || !d_assign || (total_bases > 0 && !d_bases) || total_bases < 0) return MNC_ERR_ARG;
 	if (((uintptr_t)d_bases & 15u) != 0) { set_error("d_bases must be 16-byte aligned"); return MNC_ERR_ARG; }
-	if (max_read_len < 0 || max_read_len >= (1 << 20)) { set_error("reads of 2^20 bases or more are not supported"); return MNC_ERR_UNSUPPORTED; }
+	// a call with a read of 2^20 bases or more runs wide as a whole (mnc_engine_set_long_reads)
+	const bool wide = e->long_reads && max_read_len >= (1 << QPOS_BITS);
+	if (max_read_len < 0 || (wide ? max_read_len > MNC_MAX_READ_LEN_WIDE : max_read_len >= (1 << QPOS_BITS))) {
+		set_error(e->long_reads ? "reads beyond 2^24 - 1 bases are not supported" : "reads of 2^20 bases or more are not supported (mnc_engine_set_long_reads)");
+		return MNC_ERR_UNSUPPORTED;
+	}
 	if (n_reads > (1u << 20)) { set_error("at most 2^20 reads per batch (query records hold a 20-bit read ordinal)"); return MNC_ERR_UNSUPPORTED; }
+	if (wide && n_reads > (uint32_t)WIDE_MAX_READS) { set_error("at most 2^16 reads in a call with reads of 2^20 bases or more (wide query records hold a 16-bit read ordinal)"); return MNC_ERR_UNSUPPORTED; }
 	if (total_bases >= (1LL << 40)) return MNC_ERR_UNSUPPORTED;
 	HIP_TRY(hipSetDevice(e->device));
-	e->have_batch = false, e->last_total_hits = -1;
+	e->have_batch = false, e->last_total_hits = -1, e->have_merged = false, e->cur_wide = wide;
+	// the MAPQ look-ups reach as far as the longest read can score (and exist again after a failed enlargement)
+	const int64_t logf_want = wide ? std::min<int64_t>((int64_t)e->idx->par.a * max_read_len + 1024, INT32_MAX / 8) : 1 << 21;
+	if (logf_want > e->logf_n) {
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		if (int lrc = logf_tables(e, (int)logf_want)) return lrc;
+	}
 	if (n_reads == 0) {
 		memset(&e->B, 0, sizeof(e->B));
 		e->have_batch = true, e->last_total_anchors = 0;
@@ -1340,44 +1379,11 @@ extern "C" int mnc_engine_prefetch_cancel(mnc_engine *e)
 }
 
 // ---------------------------------------------------------------- one batch, host buffers
-extern "C" int mnc_classify_batch(mnc_engine *e, const uint8_t *bases, const int64_t *offsets, uint32_t n_reads,
-                                  int min_mapq, int32_t *out_assign, mnc_hit_t *out_best, int32_t *out_nhits)
+// One pass over host arrays none of whose reads is outside the pass' limits: copy in (or take the announced
+// prefetch of these very arrays), classify, copy out.  (max_len >= 2^20 makes it the wide pass: mnc_classify_device.)
+static int classify_host(mnc_engine *e, const uint8_t *bases, const int64_t *offsets, uint32_t n_reads, int64_t total, int max_len,
+                         int min_mapq, int32_t *out_assign, mnc_hit_t *out_best, int32_t *out_nhits)
 {
-	if (!e || !offsets || !out_assign) return MNC_ERR_ARG;
-	const int64_t total = offsets[n_reads] - offsets[0];
-	if (offsets[0] != 0 || total < 0 || (total > 0 && !bases)) { set_error("offsets must start at 0 and be non-decreasing"); return MNC_ERR_ARG; }
-	int max_len = 0;
-	size_t n_over = 0;
-	for (uint32_t r = 0; r < n_reads; ++r) {
-		const int64_t l = offsets[r + 1] - offsets[r];
-		if (l < 0) { set_error("offsets must be non-decreasing"); return MNC_ERR_ARG; }
-		if (l >= (1 << 20)) ++n_over;
-		else if (l > max_len) max_len = (int)l;
-	}
-	if (n_over) {
-		// Reads of 2^20 bases or more are outside what the kernels hold (a query position is a 20-bit field of the
-		// probe's records and of the packed anchors).  index.map() takes any length (aligner.py:193, 215), so such a read
-		// must not cost the batch: it is taken out (an empty read in its place), the others are classified as ever, and
-		// it comes back as MNC_SKIPPED -- the one limit of this entry point that shows in its results.
-		std::vector<int64_t> foff((size_t)n_reads + 1);
-		std::vector<uint8_t> fb;
-		try { fb.reserve((size_t)total); } catch (const std::bad_alloc &) { return MNC_ERR_NOMEM; }
-		foff[0] = 0;
-		for (uint32_t r = 0; r < n_reads; ++r) {
-			const int64_t l = offsets[r + 1] - offsets[r];
-			if (l < (1 << 20)) fb.insert(fb.end(), bases + offsets[r], bases + offsets[r + 1]);
-			foff[r + 1] = (int64_t)fb.size();
-		}
-		const int rc = mnc_classify_batch(e, fb.empty() ? bases : fb.data(), foff.data(), n_reads, min_mapq, out_assign, out_best, out_nhits);
-		if (rc) return rc;
-		for (uint32_t r = 0; r < n_reads; ++r)
-			if (offsets[r + 1] - offsets[r] >= (1 << 20)) {
-				out_assign[r] = MNC_SKIPPED;
-				if (out_best) memset(&out_best[r], 0, sizeof(mnc_hit_t));
-				if (out_nhits) out_nhits[r] = 0;
-			}
-		return MNC_OK;
-	}
 	HIP_TRY(hipSetDevice(e->device));
 	const size_t nr = n_reads;
 	int rc = e->out_assign.ensure((nr + 1) * 4);
@@ -1417,7 +1423,125 @@ extern "C" int mnc_classify_batch(mnc_engine *e, const uint8_t *bases, const int
 	rc = mnc_engine_sync(e);
 	if (rc) return rc;
 	HIP_TRY(hipGetLastError());
-	e->h_offsets.assign(offsets, offsets + nr + 1);
+	return MNC_OK;
+}
+
+// the gated hits of the pass just made, as host arrays
+static int fetch_hits_host(mnc_engine *e, uint32_t n_reads, std::vector<int64_t> &off, std::vector<mnc_hit_t> &hits)
+{
+	int64_t n = 0;
+	int rc = mnc_engine_fetch_hits(e, nullptr, nullptr, 0, &n);
+	if (rc != MNC_OK && rc != MNC_ERR_RANGE) return rc;
+	off.assign((size_t)n_reads + 1, 0);
+	hits.resize((size_t)std::max<int64_t>(n, 1));
+	rc = mnc_engine_fetch_hits(e, off.data(), hits.data(), (int64_t)hits.size(), &n);
+	hits.resize((size_t)n);
+	return rc;
+}
+
+// A call with reads outside the usual pass' limit of 2^20 - 1 bases.  index.map() takes any length (aligner.py:193, 215),
+// so such a read must not cost the batch.  The reads within the limit are classified as ever, with an empty read in the
+// place of every other -- what they come to does not depend on the others being there.  Then, with long reads switched
+// on (mnc_engine_set_long_reads), those of up to MNC_MAX_READ_LEN_WIDE bases make a batch of their own for the wide pass,
+// and its results go back to their ordinals.  What neither pass takes comes back as MNC_SKIPPED -- the one limit of this
+// entry point that shows in its results.
+static int classify_two_passes(mnc_engine *e, const uint8_t *bases, const int64_t *offsets, uint32_t n_reads, int min_mapq,
+                               int32_t *out_assign, mnc_hit_t *out_best, int32_t *out_nhits)
+{
+	const int64_t lim = 1 << QPOS_BITS, lim_wide = e->long_reads ? (int64_t)MNC_MAX_READ_LEN_WIDE : lim - 1;
+	// The caller may have announced these arrays (mnc_engine_prefetch).  Neither pass reads them as they are, so the
+	// announcement is cancelled here, in the open -- not left to be found stale, waited for and copied again.
+	if (int rc = mnc_engine_prefetch_cancel(e)) return rc;
+	std::vector<int64_t> soff, loff, hoff_s, hoff_l;
+	std::vector<uint8_t> sb, lb;
+	std::vector<uint32_t> lord;                     // ordinals of the long reads
+	std::vector<int32_t> l_assign, l_nhits;
+	std::vector<mnc_hit_t> l_best, hits_s, hits_l;
+	int max_s = 0, max_l = 0;
+	try {
+		size_t short_total = 0, long_total = 0;
+		for (uint32_t r = 0; r < n_reads; ++r) {
+			const int64_t l = offsets[r + 1] - offsets[r];
+			if (l < lim) short_total += (size_t)l, max_s = std::max(max_s, (int)l);
+			else if (l <= lim_wide) long_total += (size_t)l, max_l = std::max(max_l, (int)l), lord.push_back(r);
+		}
+		soff.resize((size_t)n_reads + 1), loff.resize(lord.size() + 1);
+		sb.reserve(short_total + 1), lb.reserve(long_total + 1);
+		soff[0] = 0;
+		for (uint32_t r = 0; r < n_reads; ++r) {
+			if (offsets[r + 1] - offsets[r] < lim) sb.insert(sb.end(), bases + offsets[r], bases + offsets[r + 1]);
+			soff[r + 1] = (int64_t)sb.size();
+		}
+		loff[0] = 0;
+		for (size_t k = 0; k < lord.size(); ++k) {
+			lb.insert(lb.end(), bases + offsets[lord[k]], bases + offsets[lord[k] + 1]);
+			loff[k + 1] = (int64_t)lb.size();
+		}
+		l_assign.resize(lord.size() + 1), l_nhits.resize(lord.size() + 1), l_best.resize(lord.size() + 1);
+	} catch (const std::bad_alloc &) { set_error("out of host memory (a batch with reads of 2^20 bases or more)"); return MNC_ERR_NOMEM; }
+	const uint32_t n_long = (uint32_t)lord.size();
+	if (n_long > (uint32_t)WIDE_MAX_READS) { set_error("at most 2^16 reads of 2^20 bases or more in one call"); return MNC_ERR_UNSUPPORTED; }
+	int rc = classify_host(e, sb.empty() ? bases : sb.data(), soff.data(), n_reads, (int64_t)sb.size(), max_s, min_mapq, out_assign, out_best, out_nhits);
+	if (rc) return rc;
+	if (n_long) {
+		// the engine remembers one pass: the first pass' hits and counters are kept on the host, the wide pass' are merged in
+		int64_t ctr[24];
+		try {
+			if ((rc = fetch_hits_host(e, n_reads, hoff_s, hits_s))) return rc;
+			if ((rc = mnc_engine_get_counters(e, ctr, 24))) return rc;
+			if ((rc = classify_host(e, lb.data(), loff.data(), n_long, (int64_t)lb.size(), max_l, min_mapq, l_assign.data(), l_best.data(), l_nhits.data()))) return rc;
+			if ((rc = fetch_hits_host(e, n_long, hoff_l, hits_l))) return rc;
+			e->merged_off.assign((size_t)n_reads + 1, 0);
+			e->merged_hits.clear();
+			e->merged_hits.reserve(hits_s.size() + hits_l.size());
+			for (uint32_t r = 0, k = 0; r < n_reads; ++r) {
+				if (k < n_long && lord[k] == r) {
+					e->merged_hits.insert(e->merged_hits.end(), hits_l.begin() + hoff_l[k], hits_l.begin() + hoff_l[k + 1]);
+					++k;
+				} else e->merged_hits.insert(e->merged_hits.end(), hits_s.begin() + hoff_s[r], hits_s.begin() + hoff_s[r + 1]);
+				e->merged_off[r + 1] = (int64_t)e->merged_hits.size();
+			}
+		} catch (const std::bad_alloc &) { e->have_batch = false; set_error("out of host memory (gated hits of two passes)"); return MNC_ERR_NOMEM; }
+		for (uint32_t k = 0; k < n_long; ++k) {
+			out_assign[lord[k]] = l_assign[k];
+			if (out_best) out_best[lord[k]] = l_best[k];
+			if (out_nhits) out_nhits[lord[k]] = l_nhits[k];
+		}
+		memcpy(e->merged_ctr, ctr, sizeof(ctr));
+		e->have_merged = true;
+	}
+	for (uint32_t r = 0; r < n_reads; ++r)
+		if (offsets[r + 1] - offsets[r] > lim_wide) {
+			out_assign[r] = MNC_SKIPPED;
+			if (out_best) memset(&out_best[r], 0, sizeof(mnc_hit_t));
+			if (out_nhits) out_nhits[r] = 0;
+		}
+	return MNC_OK;
+}
+
+extern "C" int mnc_classify_batch(mnc_engine *e, const uint8_t *bases, const int64_t *offsets, uint32_t n_reads,
+                                  int min_mapq, int32_t *out_assign, mnc_hit_t *out_best, int32_t *out_nhits)
+{
+	if (!e || !offsets || !out_assign) return MNC_ERR_ARG;
+	const int64_t total = offsets[n_reads] - offsets[0];
+	if (offsets[0] != 0 || total < 0 || (total > 0 && !bases)) { set_error("offsets must start at 0 and be non-decreasing"); return MNC_ERR_ARG; }
+	const int64_t lim = 1 << QPOS_BITS, lim_wide = e->long_reads ? (int64_t)MNC_MAX_READ_LEN_WIDE : lim - 1;
+	int64_t max_len = 0;
+	size_t n_long = 0, n_over = 0;                  // reads for the wide pass; reads for neither
+	for (uint32_t r = 0; r < n_reads; ++r) {
+		const int64_t l = offsets[r + 1] - offsets[r];
+		if (l < 0) { set_error("offsets must be non-decreasing"); return MNC_ERR_ARG; }
+		if (l > lim_wide) ++n_over;
+		else if (l >= lim) ++n_long;
+		if (l <= lim_wide && l > max_len) max_len = l;
+	}
+	int rc;
+	// every read within the usual limit -- or every read a long one: one pass over the caller's arrays as they are
+	if (n_over == 0 && (n_long == 0 || (n_long == n_reads && n_reads <= (uint32_t)WIDE_MAX_READS)))
+		rc = classify_host(e, bases, offsets, n_reads, total, (int)max_len, min_mapq, out_assign, out_best, out_nhits);
+	else rc = classify_two_passes(e, bases, offsets, n_reads, min_mapq, out_assign, out_best, out_nhits);
+	if (rc) return rc;
+	try { e->h_offsets.assign(offsets, offsets + (size_t)n_reads + 1); } catch (const std::bad_alloc &) { e->h_offsets.clear(); }
 	return MNC_OK;
 }
 
@@ -1426,6 +1550,13 @@ extern "C" int mnc_engine_fetch_hits(mnc_engine *e, int64_t *hit_offsets, mnc_hi
 {
 	if (!e || !n_hits) return MNC_ERR_ARG;
 	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
+	if (e->have_merged) {                                   // a call of two passes (long reads): the CSR over all its reads was put together on the host
+		*n_hits = (int64_t)e->merged_hits.size();
+		if (cap < *n_hits || !hits || !hit_offsets) return MNC_ERR_RANGE;
+		memcpy(hit_offsets, e->merged_off.data(), e->merged_off.size() * 8);
+		if (*n_hits) memcpy(hits, e->merged_hits.data(), e->merged_hits.size() * sizeof(mnc_hit_t));
+		return MNC_OK;
+	}
 	HIP_TRY(hipSetDevice(e->device));
 	hipStream_t st = e->stream;
 	Batch &B = e->B;
@@ -1480,9 +1611,8 @@ extern "C" int mnc_engine_get_counters(mnc_engine *e, int64_t *c, int n)
 		if (n >= 16) c[12] = (int64_t)d[48], c[13] = (int64_t)d[49], c[14] = (int64_t)d[50], c[15] = (int64_t)d[51];
 		if (n >= 24) c[16] = (int64_t)d[6], c[17] = (int64_t)d[28], c[18] = (int64_t)d[31], c[19] = (int64_t)d[56], c[20] = (int64_t)d[62], c[21] = (int64_t)d[22];
 		if (n >= 24) c[22] = (int64_t)d[30], c[23] = (int64_t)d[52];       // the 42-cell tier: segments, anti-diagonals
-
-
 	}
+	if (e->have_merged) for (int i = 0; i < n && i < 24; ++i) c[i] += e->merged_ctr[i];   // a call of two passes (long reads): both
 	return MNC_OK;
 }
 

@@ -31,7 +31,8 @@ constexpr int PA_PRE = 16;                          // minimizers a lane fetches
 // BK: the type that holds a region number in the stage (a byte with 256 regions), OFF: a run's start in the record array
 // (32 bits whenever the batch's records fit) -- the kernel's LDS sets its occupancy: 39 KB (four workgroups a CU) with
 // 256 regions, 52 KB (three) with 1 024
-template <class BK, class OFF>
+// QB: bits of a query position in the record (device.h: QPOS_BITS, or QPOS_BITS_WIDE in the pass for reads of 2^20 bases or more)
+template <int QB, class BK, class OFF>
 __global__ __launch_bounds__(PA_THREADS) void mnc_partition_queries(Batch B)
 {
 	extern __shared__ __align__(16) uint8_t pa_smem[];
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(PA_THREADS) void mnc_partition_queries(Batch B)
 			const uint32_t rank = atomicAdd(&s_cur[b], 1u);
 			const int64_t dst = (int64_t)s_off[b] + rank;
 			const uint64_t rec = (uint64_t)pb_rest(q.x, pb_bits) | (uint64_t)(q.y & 1u) << 22 | (uint64_t)(tandem ? 1u : 0u) << 23 |
-			                     (uint64_t)(q.y >> 1) << 24 | (uint64_t)r << 44;
+			                     (uint64_t)(q.y >> 1) << 24 | (uint64_t)r << (24 + QB);
 			if (dst >= B.q_cap) *B.overflow = 1u;
 			else if (staged) { const uint32_t at = s_loc[b] + rank; s_rec[at] = rec; s_bkt[at] = (BK)b; }
 			else B.qrec[dst] = rec;
@@ -121,7 +122,9 @@ __global__ __launch_bounds__(PA_THREADS) void mnc_partition_queries(Batch B)
 // runs of 14.5 records again.  The stage holds a record in six bytes -- the read is one of 4 G, the rest is rebuilt on
 // the way out -- and the copy-out goes run by run (sixteen lanes a run), so no region number is kept per record:
 // 60 KB of LDS for G = 2 (two workgroups a CU), 108 KB for G = 4 (one: sixteen waves a CU either way).
-template <int G, class OFF>
+// (The six-byte stage keeps 20 bits of the position: the wide form writes every record directly, as a tile beyond the
+// stage does -- a read of 2^20 bases has ~190 k minimizers, twelve times the stage of G = 4.)
+template <int QB, int G, class OFF>
 __global__ __launch_bounds__(PA_THREADS * G) void mnc_partition_group(Batch B)
 {
 	constexpr int THREADS = PA_THREADS * G, STAGE = PA_STAGE * G;
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(PA_THREADS * G) void mnc_partition_group(Batch B)
 	}
 	__syncthreads();
 	const uint32_t total = s_loc[pb_n];
-	const bool staged = total <= (uint32_t)STAGE;
+	const bool staged = QB == QPOS_BITS && total <= (uint32_t)STAGE;
 	const uint32_t lr = (uint32_t)(tid >> 6);
 	uint32_t prev_hash = 0xffffffffu;
 	for (int i0 = 0; i0 < n; i0 += 64) {
@@ -192,7 +195,7 @@ __global__ __launch_bounds__(PA_THREADS * G) void mnc_partition_group(Batch B)
 			const uint32_t lo24 = pb_rest(q.x, pb_bits) | (q.y & 1u) << 22 | (tandem ? 1u : 0u) << 23, qpos = q.y >> 1;
 			if (dst >= B.q_cap) *B.overflow = 1u;
 			else if (staged) { const uint32_t at = s_loc[b] + rank; s_lo[at] = lo24 | qpos << 24; s_hi[at] = (uint16_t)((qpos >> 8 & 0xfffu) | lr << 12); }
-			else B.qrec[dst] = (uint64_t)lo24 | (uint64_t)qpos << 24 | (uint64_t)r << 44;
+			else B.qrec[dst] = (uint64_t)lo24 | (uint64_t)qpos << 24 | (uint64_t)r << (24 + QB);
 		}
 	}
 	__syncthreads();
@@ -223,7 +226,7 @@ __global__ __launch_bounds__(PA_THREADS * G) void mnc_partition_group(Batch B)
 // With 1 024 regions a region has 91 k and a run 232: workgroups that kept their 7.4 k queries (four runs a wave) had
 // EIGHT regions open per XCD -- 16 MiB -- and 64 % of the table reads missed the L2 (profiles/r03l_pmc, 62 genomes).
 // So a workgroup takes fewer queries, not more: one run a wave, 16 waves per copy of the region's filter into LDS.
-template <int THREADS, int PR_U, int RUNS>
+template <int QB, int THREADS, int PR_U, int RUNS>
 __global__ __launch_bounds__(THREADS) void mnc_probe_buckets(Batch B, uint32_t wgs_per_bucket)
 {
 	constexpr int PR_THREADS = THREADS;
@@ -302,9 +305,9 @@ __global__ __launch_bounds__(THREADS) void mnc_probe_buckets(Batch B, uint32_t w
 					const unsigned long long m = __ballot(emit);
 					if (emit) {
 						HitRec h;
-						const uint32_t qpos = (uint32_t)(rec[u] >> 24) & 0xfffffu, rd = (uint32_t)(rec[u] >> 44);
+						const uint32_t qpos = (uint32_t)(rec[u] >> 24) & ((1u << QB) - 1u), rd = (uint32_t)(rec[u] >> (24 + QB));
 						h.val = val[u];
-						h.qinfo = qpos << 1 | ((uint32_t)(rec[u] >> 22) & 1u) | (rd - read0) << 21;
+						h.qinfo = qpos << 1 | ((uint32_t)(rec[u] >> 22) & 1u) | (rd - read0) << (QB + 1);
 						h.cnt = cnt[u] >= mid_occ ? HIT_HIGH : (cnt[u] | ((uint32_t)(rec[u] >> 23) & 1u) << 31);
 						B.bhits[q0 + n_out + __popcll(m & lt)] = h;
 					}
@@ -322,6 +325,7 @@ __global__ __launch_bounds__(THREADS) void mnc_probe_buckets(Batch B, uint32_t w
 // one wave per read finishes hit_cnt / an_cnt / rep_len.
 constexpr int CO_THREADS = 1024;
 
+template <int QB>
 __global__ __launch_bounds__(CO_THREADS) void mnc_collect_hits(Batch B)
 {
 	__shared__ int64_t s_start[PB_N_MAX];
@@ -346,10 +350,10 @@ __global__ __launch_bounds__(CO_THREADS) void mnc_collect_hits(Batch B)
 		const HitRec *src = B.bhits + s_start[b];
 		for (uint32_t f = tid & 63; f < cnt; f += 64) {
 			HitRec h = src[f];
-			const uint32_t lr = (h.qinfo >> 21) & (SUPER_READS - 1);
+			const uint32_t lr = (h.qinfo >> (QB + 1)) & (SUPER_READS - 1);
 			const uint32_t r = read0 + lr;
 			const int64_t off = B.offsets[r];
-			h.qinfo &= 0x1fffffu;
+			h.qinfo &= (2u << QB) - 1u;
 			if (h.cnt == HIT_HIGH) {
 				const int64_t cap = B.offsets[r + 1] - off;
 				B.hits[off + cap - 1 - atomicAdd(&s_hi[lr], 1u)] = h;
@@ -394,53 +398,68 @@ __global__ __launch_bounds__(CO_THREADS) void mnc_collect_hits(Batch B)
 	}
 }
 
-template <int G, class OFF>
+template <int QB, int G, class OFF>
 static void launch_partition_group(const Batch &B, hipStream_t st)
 {
 	const size_t lds = (size_t)PA_STAGE * G * 6 + (size_t)B.pb_n * (sizeof(OFF) + 8) + 16;
 	const uint32_t n_groups = (B.n_tiles + G - 1) / G;
-	hipLaunchKernelGGL((mnc_partition_group<G, OFF>), dim3((n_groups + 7) / 8 * 8), dim3(PA_THREADS * G), lds, st, B);
+	hipLaunchKernelGGL((mnc_partition_group<QB, G, OFF>), dim3((n_groups + 7) / 8 * 8), dim3(PA_THREADS * G), lds, st, B);
 }
 
 // dynamic LDS above 64 KiB is opted into once per function (and device: called when an engine is made)
-int partition_prepare()
+template <int QB>
+static hipError_t partition_prepare_as()
 {
 	const int lds = PA_STAGE * 4 * 6 + PB_N_MAX * 16 + 16;
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<4, uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-	if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<4, int64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<QB, 4, uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+	if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<QB, 4, int64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 	// (two tiles a workgroup at 1 024 regions -- MNC_PARTITION_G=2 -- with 64-bit run offsets is 65 552 bytes: above 64 KiB too)
-	if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<2, uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-	if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<2, int64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+	if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<QB, 2, uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+	if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mnc_partition_group<QB, 2, int64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+	return e;
+}
+
+int partition_prepare()
+{
+	hipError_t e = partition_prepare_as<QPOS_BITS>();
+	if (e == hipSuccess) e = partition_prepare_as<QPOS_BITS_WIDE>();
 	if (e != hipSuccess) { set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return MNC_ERR_HIP; }
 	return MNC_OK;
 }
 
-void launch_partition(const Batch &B, hipStream_t st)
+template <int QB>
+static void launch_partition_as(const Batch &B, hipStream_t st)
 {
-	if (B.n_tiles == 0) return;
 	const bool small = B.q_cap < (1LL << 32);
 	// more than 256 regions: a workgroup over regions / 256 tiles (MNC_PARTITION_TILES=1: the one-tile form, for comparison)
 	static const bool one_tile = getenv("MNC_PARTITION_TILES") && atoi(getenv("MNC_PARTITION_TILES")) == 1;
 	static const int force_g = getenv("MNC_PARTITION_G") ? atoi(getenv("MNC_PARTITION_G")) : 0;   // (2: two tiles a workgroup at 1 024 regions too, for comparison)
 	if (B.pb_n > 256 && !one_tile) {
-		if (B.pb_n <= 512 || force_g == 2) { if (small) launch_partition_group<2, uint32_t>(B, st); else launch_partition_group<2, int64_t>(B, st); }
-		else { if (small) launch_partition_group<4, uint32_t>(B, st); else launch_partition_group<4, int64_t>(B, st); }
+		if (B.pb_n <= 512 || force_g == 2) { if (small) launch_partition_group<QB, 2, uint32_t>(B, st); else launch_partition_group<QB, 2, int64_t>(B, st); }
+		else { if (small) launch_partition_group<QB, 4, uint32_t>(B, st); else launch_partition_group<QB, 4, int64_t>(B, st); }
 		return;
 	}
 	const size_t fixed = (size_t)PA_STAGE * 8 + (size_t)B.pb_n * (small ? 12 : 16) + 16, bk = (size_t)PA_STAGE * (B.pb_n <= 256 ? 1 : 2);
 	const dim3 grid((B.n_tiles + 7) / 8 * 8);
-	if (B.pb_n <= 256 && small) hipLaunchKernelGGL((mnc_partition_queries<uint8_t, uint32_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
-	else if (B.pb_n <= 256) hipLaunchKernelGGL((mnc_partition_queries<uint8_t, int64_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
-	else if (small) hipLaunchKernelGGL((mnc_partition_queries<uint16_t, uint32_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
-	else hipLaunchKernelGGL((mnc_partition_queries<uint16_t, int64_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
+	if (B.pb_n <= 256 && small) hipLaunchKernelGGL((mnc_partition_queries<QB, uint8_t, uint32_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
+	else if (B.pb_n <= 256) hipLaunchKernelGGL((mnc_partition_queries<QB, uint8_t, int64_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
+	else if (small) hipLaunchKernelGGL((mnc_partition_queries<QB, uint16_t, uint32_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
+	else hipLaunchKernelGGL((mnc_partition_queries<QB, uint16_t, int64_t>), grid, dim3(PA_THREADS), fixed + bk, st, B);
 }
 
-template <int THREADS, int PR_U, int RUNS>
+void launch_partition(const Batch &B, hipStream_t st)
+{
+	if (B.n_tiles == 0) return;
+	if (B.qpos_bits == QPOS_BITS_WIDE) launch_partition_as<QPOS_BITS_WIDE>(B, st);
+	else launch_partition_as<QPOS_BITS>(B, st);
+}
+
+template <int QB, int THREADS, int PR_U, int RUNS>
 static void launch_probe_as(const Batch &B, hipStream_t st)
 {
 	const uint32_t per_wg = (THREADS / 64) * RUNS;                              // super-tiles a workgroup takes
 	const uint32_t W = (B.n_super + per_wg - 1) / per_wg;
-	hipLaunchKernelGGL((mnc_probe_buckets<THREADS, PR_U, RUNS>), dim3(B.pb_n * W), dim3(THREADS), 0, st, B, W);
+	hipLaunchKernelGGL((mnc_probe_buckets<QB, THREADS, PR_U, RUNS>), dim3(B.pb_n * W), dim3(THREADS), 0, st, B, W);
 }
 
 void launch_probe(const Batch &B, hipStream_t st)
@@ -448,14 +467,18 @@ void launch_probe(const Batch &B, hipStream_t st)
 	if (B.n_super == 0) return;
 	// (1 024 regions: 16 waves x one run measured against 8 x 1 and 4 x 1 -- 0.73 / 0.79 / 1.02 ms at 62 genomes: fewer
 	// queries per copy of the filter cost more than the locality gives, profiles/r03n_probe_shapes.txt)
-	if (B.pb_n <= 512) launch_probe_as<512, 8, 1>(B, st);
-	else launch_probe_as<1024, 4, 1>(B, st);
+	if (B.qpos_bits == QPOS_BITS_WIDE) {
+		if (B.pb_n <= 512) launch_probe_as<QPOS_BITS_WIDE, 512, 8, 1>(B, st);
+		else launch_probe_as<QPOS_BITS_WIDE, 1024, 4, 1>(B, st);
+	} else if (B.pb_n <= 512) launch_probe_as<QPOS_BITS, 512, 8, 1>(B, st);
+	else launch_probe_as<QPOS_BITS, 1024, 4, 1>(B, st);
 }
 
 void launch_collect(const Batch &B, hipStream_t st)
 {
 	if (B.n_super == 0) return;
-	hipLaunchKernelGGL(mnc_collect_hits, dim3(B.n_super), dim3(CO_THREADS), 0, st, B);
+	if (B.qpos_bits == QPOS_BITS_WIDE) hipLaunchKernelGGL(mnc_collect_hits<QPOS_BITS_WIDE>, dim3(B.n_super), dim3(CO_THREADS), 0, st, B);
+	else hipLaunchKernelGGL(mnc_collect_hits<QPOS_BITS>, dim3(B.n_super), dim3(CO_THREADS), 0, st, B);
 }
 
 } // namespace mnc

@@ -145,6 +145,12 @@ def default_device():
     return 0
 
 
+def long_reads_default():
+    """MONICA_AMD_LONG_READS=1: reads of 2^20 bases or more are classified (`mnc_engine_set_long_reads`); anything
+    else, or unset: they come back SKIPPED, as ever."""
+    return os.environ.get("MONICA_AMD_LONG_READS", "").strip() == "1"
+
+
 def _build_device(device):
     """The device that sketches and sorts an index being built (csrc/k_idxbuild.hip), or None for the host builder
     when no device is visible (building an index is not part of the classified path; both give the same index)."""
@@ -194,8 +200,10 @@ class Aligner:
 
     def __init__(self, fn_idx_in=None, preset=None, k=None, w=None, min_cnt=None, min_chain_score=None,
                  min_dp_score=None, bw=None, best_n=None, n_threads=3, fn_idx_out=None, max_frag_len=None,
-                 extra_flags=None, seq=None, scoring=None, device=None):
+                 extra_flags=None, seq=None, scoring=None, device=None, long_reads=None):
         self._index = None
+        # reads of 2^20 bases or more (up to _capi.MAX_READ_LEN_WIDE): classified when on; None: by MONICA_AMD_LONG_READS
+        self._long_reads = long_reads_default() if long_reads is None else bool(long_reads)
         self._borrowed = []
         self._tls = threading.local()
         self._device = default_device() if device is None else int(device)
@@ -274,6 +282,8 @@ class Aligner:
                         raise
                     release_idle(self._index)
                     e = _capi.Engine(self._index, self._device)
+            # every engine this object hands out, a pooled one that was rebound included
+            e.set_long_reads(self._long_reads)
             self._tls.engine = e
             with _INDEX_CACHE_LOCK:
                 self._borrowed.append(e)
@@ -287,6 +297,8 @@ class Aligner:
                     # only engines of a cached part go back: one bound to an uncached index would keep that index alive
                     room = max(0, _POOL_MAX_PER_DEVICE - len(pool)) if _is_cached(self._index) else 0
                     keep, rest = self._borrowed[:room], self._borrowed[room:]
+                    for eng in keep:                           # back to the pool as it came: the switch is this object's
+                        eng.set_long_reads(False)
                     pool.extend(keep)
                     self._borrowed = []
                 for eng in rest:                               # not pooled: release the HBM now
