@@ -308,7 +308,18 @@ int mnc_engine_dump_tables(mnc_engine *eng, void *dst, int64_t cap_bytes, int64_
 #define MNC_DUMP_SEGS       12 /* the alignment stage's kernel calls (one per ksw_extd2 call of mm_align1): 24 int32
                                   {read, region slot, kind 0 left ext / 1 gap / 2 right ext, rid, rev, ts, tlen,
                                   qs, qlen, w, zdrop, flag, seed, kernel class, n_cigar, zdropped, zdrop_code,
-                                  max, max_t, max_q, score, reach_end, mqe_t, pad} + int64 CIGAR offset; tools only */
+                                  max, max_t, max_q, score, reach_end, mqe_t, pad} + int64 CIGAR offset (first word of the
+                                  call's CIGAR in MNC_DUMP_SEG_CIGARS); MNC_CONTRACT_DP only.  tests/segments.py replays
+                                  every call on the CPU oracle from it; tools/ read it as well.  Result fields a later
+                                  step never reads for that kind and outcome may be left as planned (max 0, max_t / max_q /
+                                  mqe_t -1, score -2^30): the table in tests/segments.py                              */
+#define MNC_DUMP_SEG_CIGARS 13 /* the per-call CIGAR pool of those calls: uint32 len<<4|op (0 M, 1 I, 2 D), every word
+                                  handed out in the last batch; a call's CIGAR is words [cig_off, cig_off + n_cigar), in the
+                                  order ksw_extd2 returns them for that call: first to last operation of the sequences AS
+                                  PASSED to the kernel for a gap filling and a right extension; for a left extension (both
+                                  sequences reversed, KSW_EZ_REV_CIGAR) last to first of the reversed pair, i.e. left to
+                                  right on the read -- so that a region's CIGAR is its calls' words back to back.  Calls
+                                  land in the pool in the order the kernels finished them.  MNC_CONTRACT_DP only           */
 typedef struct {
 	int32_t id, parent, rid, rev, rs, re, qs, qe, score, score0, cnt, as, mlen, blen,
 	        subsc, n_sub, mapq;

@@ -38,7 +38,7 @@ N_STAGES = 22
  STAGE_BACKTRACK, STAGE_REGIONS, STAGE_GATHER, STAGE_DP_PLAN, STAGE_DP_ALIGN, STAGE_DP_STITCH,
  STAGE_DP_POST, STAGE_DP_FILL, STAGE_DP_FILL_T1, STAGE_DP_FILL_T2, STAGE_DP_FILL_T3, STAGE_DP_EXT, STAGE_DP_FILL_TM, STAGE_DP_LFILL) = range(N_STAGES)
 (DUMP_MINIMIZERS, DUMP_MZ_OFFSETS, DUMP_ANCHORS, DUMP_AN_OFFSETS, DUMP_CHAIN_F, DUMP_CHAIN_P,
- DUMP_CHAIN_V, DUMP_REGS, DUMP_REG_OFFSETS, DUMP_REP_LEN, DUMP_CIGARS, DUMP_SEGS) = range(1, 13)
+ DUMP_CHAIN_V, DUMP_REGS, DUMP_REG_OFFSETS, DUMP_REP_LEN, DUMP_CIGARS, DUMP_SEGS, DUMP_SEG_CIGARS) = range(1, 14)
 SEG_DTYPE = np.dtype([(k, np.int32) for k in ("read", "reg", "kind", "rid", "rev", "ts", "tlen", "qs", "qlen", "w", "zdrop", "flag",
                                               "ai", "big", "n_cigar", "zdropped", "zdrop_code", "max", "max_t", "max_q", "score",
                                               "reach_end", "mqe_t", "pad")] + [("cig_off", np.int64)])

@@ -1720,6 +1720,17 @@ extern "C" int mnc_engine_dump(mnc_engine *e, int what, void *dst, int64_t cap_b
 		if (n_seg) HIP_TRY(hipMemcpy(dst, B.segs, (size_t)*n_bytes, hipMemcpyDeviceToHost));
 		return MNC_OK;
 	}
+	case MNC_DUMP_SEG_CIGARS: {
+		// the per-call CIGAR pool those calls wrote (Seg.cig_off / n_cigar index it): the words handed out so far
+		if (B.contract != MNC_CONTRACT_DP || !e->dp_ctr.p) { set_error("segment CIGARs exist under MNC_CONTRACT_DP only"); return MNC_ERR_ARG; }
+		unsigned long long n_words = 0;
+		HIP_TRY(hipMemcpy(&n_words, e->dp_ctr.as<unsigned long long>() + 1, 8, hipMemcpyDeviceToHost));
+		if ((long long)n_words > B.cig_seg_cap) n_words = (unsigned long long)B.cig_seg_cap;
+		*n_bytes = (int64_t)(n_words * 4);
+		if (!dst || cap_bytes < *n_bytes) return MNC_ERR_RANGE;
+		if (n_words) HIP_TRY(hipMemcpy(dst, B.cig_seg, (size_t)*n_bytes, hipMemcpyDeviceToHost));
+		return MNC_OK;
+	}
 	case MNC_DUMP_REP_LEN:
 		*n_bytes = (int64_t)nr * 4;
 		if (!dst || cap_bytes < *n_bytes) return MNC_ERR_RANGE;

@@ -407,11 +407,7 @@ def test_flanks_that_zdrop_after_the_query_has_ended(capi, oracle, world):
     rng = np.random.default_rng(123)
     junk = lambda n: util.ACGT[rng.integers(0, 4, n)]
 
-    def sparse(piece):                    # ~90 % identity without a 15-mer in common: a base changed every ten
-        p = piece.copy()
-        for i in range(4, len(p), 10):
-            p[i] = util.ACGT[(np.searchsorted(util.ACGT, p[i]) + 1 + rng.integers(0, 3)) % 4]
-        return p
+    sparse = lambda piece: util.sparse(piece, rng)      # ~90 % identity without a 15-mer in common: a base changed every ten
 
     reads = []
     for k, (nj, ns) in enumerate([(120, 40), (160, 60), (190, 60), (220, 30), (240, 10), (100, 90), (180, 70), (250, 0)]):

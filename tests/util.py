@@ -16,6 +16,14 @@ def revcomp(a):
     return COMP[np.asarray(a, dtype=np.uint8)][::-1].copy()
 
 
+def sparse(piece, rng):
+    """~90 % identity without a 15-mer in common: a base changed every ten (bases outside ACGT are left alone)."""
+    p = piece.copy()
+    for i in range(4, len(p), 10):
+        p[i] = ACGT[(np.searchsorted(ACGT, p[i]) + 1 + rng.integers(0, 3)) % 4]
+    return p
+
+
 def small_genomes(n=4, min_len=200_000, max_len=300_000, seed=0x20):
     return synth.genome_set(n, seed=seed, min_len=min_len, max_len=max_len)
 
