@@ -171,6 +171,11 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   bases                                        in the plan, bases read in place by the stitch kernel)
  *   a batch that outgrows a pool (query records, exact: the batch is redone with more room (mnc_engine_get_counters [7] counts
  *   segments, CIGAR words, region slots)         the passes); MNC_ERR_NOMEM when HBM itself is exhausted
+ *   alignment records after a call that ran      mnc_engine_export_alignments: MNC_ERR_UNSUPPORTED (the engine holds the wide
+ *   both the usual and the wide pass             pass alone); classify the two groups in separate calls.  A call whose reads
+ *                                                are all long exports like any other
+ *   cs / MD under MNC_CONTRACT_CHAIN             mnc_engine_export_alignments: MNC_ERR_ARG (no base-level alignment: records
+ *                                                only, n_cigar = 0)
  */
 
 /* ---------------------------------------------------------------- classify
@@ -330,6 +335,60 @@ typedef struct {
 } mnc_reg_t;
 int mnc_engine_dump(mnc_engine *eng, int what, void *dst, int64_t cap_bytes, int64_t *n_bytes);
 
+/* ---------------------------------------------------------------- alignment records
+ * Everything index.map() yields per hit (aligner.py:193, 215; mappy's q_st q_en r_st r_en strand mlen blen mapq NM
+ * cigar, and cs / MD on request) for the whole of the last classified batch, made on the device by a stage that runs
+ * only when asked for (csrc/k_export.hip): without an export call a batch costs not one more kernel, allocation or byte.
+ *
+ *   mnc_engine_export_alignments   builds, in HBM pools the engine owns: one mnc_aln_t per region of every read's list
+ *                                  (secondaries, Z-drop splits and inversion regions alike; read order, within a read the
+ *                                  order of MNC_DUMP_REGS = the order mappy yields hits), the CSR over reads, the CIGARs
+ *                                  back to back, and -- `what` = MNC_ALN_CS | MNC_ALN_MD -- the cs (short form, no "cs:Z:")
+ *                                  and MD strings of minimap2 2.17's write_cs_core / write_MD_core.  Works on the engine's
+ *                                  stream from the last batch as it stands in HBM (regions, region CIGARs, the batch's
+ *                                  bases, the contig bases), so after mnc_classify_device the caller's d_bases /
+ *                                  d_offsets must still be there.  The host waits twice for a few bytes (the record count
+ *                                  sizes the record pool, the three pool sizes the rest); the pass that fills the pools is
+ *                                  left running on the stream.  Any size pointer may be NULL.
+ *   mnc_engine_fetch_alignments    copies them to the host.  MNC_ERR_RANGE when any cap is below what export reported
+ *                                  (nothing is copied then); a pool pointer may be NULL when its size is 0.
+ *   mnc_engine_alignments_device   the pools themselves (device pointers; any out pointer may be NULL), valid until the
+ *                                  next classify or export call on the engine; ordered on the engine's stream.
+ * Under MNC_CONTRACT_CHAIN there are records only (n_cigar = 0; blen / mlen / nm of the chain) and asking for cs / MD is
+ * MNC_ERR_ARG.  After a call that ran both the usual and the wide pass (a mixed batch with mnc_engine_set_long_reads(1))
+ * the engine holds the wide pass alone: MNC_ERR_UNSUPPORTED -- classify the two groups in separate calls.
+ * Strand: qs / qe are forward-strand read coordinates (mappy's q_st / q_en).  The CIGAR, cs and MD run left to right on
+ * the contig; for rev = 1 the query side is the reverse complement of the read, i.e. column 0 faces read base qe - 1. */
+typedef struct {
+	int32_t read;              /* ordinal of the read in the call                                  */
+	int32_t rid, rev;
+	int32_t qs, qe, rs, re;    /* as mnc_reg_t: mappy's q_st q_en r_st r_en                         */
+	int32_t mapq, mlen, blen, nm;   /* nm = blen - mlen + n_ambi                                    */
+	int32_t score, cnt;        /* mnc_reg_t.score, .cnt                                            */
+	int32_t dp_score, dp_max, n_ambi;
+	int32_t flags;             /* bit 0 primary (id == parent), bit 1 passes the gate of the call
+	                              (primary and mapq >= min_mapq), bits 8.. = mnc_reg_t.flags << 8   */
+	int32_t n_cigar;
+	int64_t cigar_off;         /* words, into the CIGAR pool (len<<4|op, 0 M 1 I 2 D)              */
+	int64_t cs_off, md_off;    /* bytes, into the cs / MD pools; strings are NOT NUL-terminated     */
+	int32_t cs_len, md_len;    /* 0 when not asked for                                             */
+} mnc_aln_t;
+
+#define MNC_ALN_CS 1
+#define MNC_ALN_MD 2
+int mnc_engine_export_alignments(mnc_engine *eng, int what,
+        int64_t *n_aln, int64_t *n_cigar_words, int64_t *n_cs_bytes, int64_t *n_md_bytes);
+int mnc_engine_fetch_alignments(mnc_engine *eng, int64_t *aln_offsets /* n_reads+1, may be NULL */,
+        mnc_aln_t *alns, int64_t cap_aln, uint32_t *cigar, int64_t cap_cigar,
+        char *cs, int64_t cap_cs, char *md, int64_t cap_md);
+int mnc_engine_alignments_device(mnc_engine *eng, const int64_t **d_aln_offsets, const mnc_aln_t **d_alns,
+        const uint32_t **d_cigar, const char **d_cs, const char **d_md);
+/* device time of the last export (count pass + scans + write pass), with mnc_engine_set_profiling on; waits for it */
+int mnc_engine_export_ms(mnc_engine *eng, double *ms);
+/* mappy.Aligner.seq(): bases [start, end) of contig rid as "ACGTN" (not NUL-terminated); MNC_ERR_ARG when rid or the
+ * interval is out of range (0 <= start <= end <= contig length) */
+int mnc_index_getseq(const mnc_index *idx, int rid, int64_t start, int64_t end, char *out /* end-start bytes, "ACGTN" */);
+
 /* ---------------------------------------------------------------- FASTQ batches and read routing
  * Replaces the per-record Biopython objects of the reference's loop:
  * SeqIO.parse(sample, 'fastq') + str(seq_record.seq) (monica/genomes/aligner.py:191-193,
@@ -367,6 +426,16 @@ int mnc_fastq_title(const mnc_fastq *fq, uint32_t r, const char **title, uint32_
 #define MNC_TO_FOCUS     8
 int mnc_fastq_route(const mnc_fastq *fq, const uint8_t *dest, const int32_t *label,
                     const char *const *labels, int n_labels, const char *const *paths);
+/* Append one PAF line per alignment record of the batch (mnc_engine_fetch_alignments' arrays, host) to `path` -- what
+ * `minimap2 -c` prints for the hits index.map() yields: read name (the title's first word), read length, qs, qe, + / -,
+ * contig name, contig length, rs, re, mlen, blen, mapq, then tp:A:P|S cm:i:<cnt> s1:i:<score> NM:i: AS:i:<dp_score>
+ * ms:i:<dp_max> nn:i:<n_ambi>, then cg:Z: / cs:Z: / MD:Z: for each of cigar / cs / md that is not NULL.
+ * flags bit 0: primary records only.  MNC_ERR_IO when the file cannot be opened or written. */
+#define MNC_PAF_PRIMARY_ONLY 1
+int mnc_fastq_write_paf(const mnc_fastq *fq, const mnc_index *idx,
+        const int64_t *aln_offsets, const mnc_aln_t *alns,
+        const uint32_t *cigar, const char *cs, const char *md,
+        int flags, const char *path);
 
 /* ---------------------------------------------------------------- hits carried across index parts
  * Replaces the `sample_hits` dict and its <sample>_hits.pkl (aligner.py:184-188, 196-203,

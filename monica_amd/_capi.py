@@ -30,6 +30,14 @@ REG_DTYPE = np.dtype([("id", "<i4"), ("parent", "<i4"), ("rid", "<i4"), ("rev", 
                       ("mapq", "<i4"), ("hash", "<u4"),
                       ("dp_score", "<i4"), ("dp_max", "<i4"), ("dp_max2", "<i4"), ("n_ambi", "<i4"),
                       ("n_cigar", "<i4"), ("flags", "<i4")])
+# mnc_aln_t: one alignment record of Engine.alignments() (104 bytes, no padding)
+ALN_DTYPE = np.dtype([(k, "<i4") for k in ("read", "rid", "rev", "qs", "qe", "rs", "re", "mapq", "mlen", "blen", "nm", "score", "cnt",
+                                           "dp_score", "dp_max", "n_ambi", "flags", "n_cigar")]
+                     + [("cigar_off", "<i8"), ("cs_off", "<i8"), ("md_off", "<i8"), ("cs_len", "<i4"), ("md_len", "<i4")])
+assert ALN_DTYPE.itemsize == 104
+ALN_CS, ALN_MD = 1, 2
+ALN_PRIMARY, ALN_GATED = 1, 2           # mnc_aln_t.flags bits 0 / 1; bits 8.. are mnc_reg_t.flags << 8
+PAF_PRIMARY_ONLY = 1
 MZ_DTYPE = np.dtype([("hash", "<u4"), ("pos_strand", "<u4")])
 ANCHOR_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8")])
 
@@ -64,6 +72,8 @@ EXPORTS = [
     "mnc_hitmap_create", "mnc_hitmap_load", "mnc_hitmap_save", "mnc_hitmap_free", "mnc_hitmap_size",
     "mnc_hitmap_update", "mnc_hitmap_n_names", "mnc_hitmap_name", "mnc_host_alloc", "mnc_host_free", "mnc_host_set_io_workers",
     "mnc_synth_genome", "mnc_synth_diverge", "mnc_synth_reads", "mnc_synth_reads_device", "mnc_version",
+    "mnc_engine_export_alignments", "mnc_engine_fetch_alignments", "mnc_engine_alignments_device", "mnc_engine_export_ms",
+    "mnc_index_getseq", "mnc_fastq_write_paf",
 ]
 
 
@@ -189,6 +199,12 @@ def lib():
     sig("mnc_host_alloc", vp, [C.c_size_t])
     sig("mnc_host_free", None, [vp])
     sig("mnc_host_set_io_workers", i32, [i32])
+    sig("mnc_engine_export_alignments", i32, [vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)])
+    sig("mnc_engine_fetch_alignments", i32, [vp, vp, vp, i64, vp, i64, vp, i64, vp, i64])
+    sig("mnc_engine_alignments_device", i32, [vp, pp, pp, pp, pp, pp])
+    sig("mnc_engine_export_ms", i32, [vp, C.POINTER(C.c_double)])
+    sig("mnc_index_getseq", i32, [vp, i32, i64, i64, vp])
+    sig("mnc_fastq_write_paf", i32, [vp, vp, vp, vp, vp, vp, vp, i32, cp])
     _LIB = L
     return L
 
@@ -357,6 +373,13 @@ class Index:
     def set_mid_occ(self, v):
         check(lib().mnc_index_set_mid_occ(self._h, int(v)))
 
+    def getseq(self, rid, start=0, end=None):
+        """Bases [start, end) of contig `rid` as bytes over "ACGTN" (`mnc_index_getseq`; MncError ERR_ARG out of range)."""
+        end = (self.contig_lens[rid] if 0 <= rid < len(self.contig_lens) else 0) if end is None else int(end)
+        buf = C.create_string_buffer(max(end - int(start), 1))
+        check(lib().mnc_index_getseq(self._h, int(rid), int(start), end, buf))
+        return buf.raw[:max(end - int(start), 0)]
+
     def dump(self):
         n = C.c_int64(0)
         lib().mnc_index_dump(self._h, None, None, 0, C.byref(n))
@@ -470,6 +493,44 @@ class Engine:
         hits = np.zeros(max(n.value, 1), dtype=HIT_DTYPE)
         check(lib().mnc_engine_fetch_hits(self._h, off.ctypes.data, hits.ctypes.data, len(hits), C.byref(n)))
         return off, hits[:n.value]
+
+    def export_alignments(self, cs=False, MD=False):
+        """`mnc_engine_export_alignments`: build the records (and cs / MD) of the last batch in HBM; returns the four
+        sizes (records, CIGAR words, cs bytes, MD bytes).  The pools stay on the device until the next classify / export."""
+        n = [C.c_int64(0) for _ in range(4)]
+        check(lib().mnc_engine_export_alignments(self._h, (ALN_CS if cs else 0) | (ALN_MD if MD else 0), *[C.byref(x) for x in n]))
+        return tuple(int(x.value) for x in n)
+
+    def fetch_alignments(self, sizes):
+        """`mnc_engine_fetch_alignments` into fresh arrays of exactly the exported sizes."""
+        n_aln, n_cig, n_cs, n_md = sizes
+        off = np.zeros(self.n_reads + 1, dtype=np.int64)
+        alns = np.zeros(n_aln, dtype=ALN_DTYPE)
+        cig = np.zeros(n_cig, dtype=np.uint32)
+        cs = np.zeros(n_cs, dtype=np.uint8)
+        md = np.zeros(n_md, dtype=np.uint8)
+        check(lib().mnc_engine_fetch_alignments(self._h, off.ctypes.data, alns.ctypes.data if n_aln else None, n_aln,
+                                                cig.ctypes.data if n_cig else None, n_cig, cs.ctypes.data if n_cs else None, n_cs,
+                                                md.ctypes.data if n_md else None, n_md))
+        return off, alns, cig, cs, md
+
+    def alignments(self, cs=False, MD=False):
+        """Everything `index.map()` yields for the last batch, as flat arrays: (offsets[n_reads + 1], records (ALN_DTYPE),
+        cigar words (len << 4 | op), cs bytes, md bytes).  Record i of read r: offsets[r] <= i < offsets[r + 1]; its CIGAR is
+        cigar[cigar_off : cigar_off + n_cigar], its strings cs[cs_off : cs_off + cs_len] / md[md_off : md_off + md_len]."""
+        return self.fetch_alignments(self.export_alignments(cs, MD))
+
+    def alignments_device(self):
+        """Device addresses (ints, 0 for an empty pool) of the exported pools: (offsets, records, cigar, cs, md)."""
+        p = [C.c_void_p() for _ in range(5)]
+        check(lib().mnc_engine_alignments_device(self._h, *[C.byref(x) for x in p]))
+        return tuple(int(x.value or 0) for x in p)
+
+    def export_ms(self):
+        """Device time span of the last export (with profiling on)."""
+        ms = C.c_double(0)
+        check(lib().mnc_engine_export_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def set_profiling(self, on=True):
         check(lib().mnc_engine_set_profiling(self._h, 1 if on else 0))
@@ -637,6 +698,18 @@ class FastqReader:
         ap = (C.c_char_p * 4)(*[(_b(x) if x is not None else None) for x in paths])
         check(lib().mnc_fastq_route(self._h, dest.ctypes.data, lab.ctypes.data if lab is not None else None,
                                     al, len(bl), ap))
+
+    def write_paf(self, index, offsets, records, path, cigar=None, cs=None, md=None, primary_only=False):
+        """Append one PAF line per alignment record of this batch (`Engine.alignments()` of its classify call) to `path`;
+        cg:Z: / cs:Z: / MD:Z: for each pool given."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        records = np.ascontiguousarray(records, dtype=ALN_DTYPE)
+        assert len(offsets) == self.n + 1 and int(offsets[-1]) <= len(records)
+        pools = [None if p is None else np.ascontiguousarray(p, dtype=t) for p, t in ((cigar, np.uint32), (cs, np.uint8), (md, np.uint8))]
+        keep = [np.zeros(1, dtype=p.dtype) if p is not None and p.size == 0 else p for p in pools]     # an empty pool is still "given"
+        check(lib().mnc_fastq_write_paf(self._h, index._h, offsets.ctypes.data, records.ctypes.data if len(records) else None,
+                                        *[(p.ctypes.data if p is not None else None) for p in keep],
+                                        PAF_PRIMARY_ONLY if primary_only else 0, _b(path)))
 
     def close(self):
         if getattr(self, "_h", None):

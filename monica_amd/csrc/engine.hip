@@ -91,6 +91,11 @@ constexpr long long DP_STATE_SMALL = 96 * 1024, DP_P_SMALL = 1 << 20, DP_CIG_SMA
 constexpr long long DP_STATE_BIG = 13 * 32768, DP_P_BIG = 8LL << 20, DP_CIG_BIG = 65536;       // 768 slots of 9 MB: any extension (max_gap 5000 on both sides: 7.7 MB of direction bytes)
 constexpr long long DP_STATE_HUGE = 13 * 32768, DP_P_HUGE = 256LL << 20, DP_CIG_HUGE = 65536;   // and 8 of 257 MB for anything up to max_sw_mat
 void launch_gather_hits(const Batch &B, const mnc_hit_t *gated, const int64_t *hit_off, mnc_hit_t *out, hipStream_t st);
+// alignment records (k_export.hip)
+void launch_export_records(const Batch &B, const int64_t *aln_off, mnc_aln_t *alns, int64_t n_aln, hipStream_t st);
+void launch_export_scan(const mnc_aln_t *alns, int64_t n_aln, int field, int64_t *out, int64_t *sums, hipStream_t st);
+void launch_export_strings(const Batch &B, bool write, mnc_aln_t *alns, int64_t n_aln, const int64_t *cig_off, const int64_t *cs_off,
+                           const int64_t *md_off, uint32_t *cigar, char *cs, char *md, int what, hipStream_t st);
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
@@ -452,6 +457,12 @@ struct mnc_engine {
 	std::vector<int64_t> merged_off;
 	std::vector<mnc_hit_t> merged_hits;
 	int64_t merged_ctr[24]{};                // the first pass' counters (added to the wide pass' own)
+	// alignment records of the last batch (mnc_engine_export_alignments): pools that grow on demand and are reused
+	Buf ex_off, ex_alns, ex_coff, ex_csoff, ex_mdoff, ex_sums, ex_cigar, ex_cs, ex_md;
+	bool ex_valid = false;
+	int64_t ex_n_reads = 0, ex_n_aln = 0, ex_n_cig = 0, ex_n_cs = 0, ex_n_md = 0;
+	hipEvent_t ev_ex[2]{};                   // around an export (made on first use, with profiling on)
+	bool ev_ex_used = false;
 	int debug = 0;                           // bit mask (tests): 2 stress build of the chaining ring, 4 displacement bytes read from HBM, 0x10000 alignment kernels one at a time (with stage timers), 0x200000 the stitch kernel reads bases in place (its form for regions beyond its LDS)
 	// last batch
 	Batch B{};
@@ -566,7 +577,8 @@ template <class F> static void engine_bufs(mnc_engine *e, F f)
 	               &e->packed, &e->mz, &e->hits, &e->hist_tm, &e->q_off, &e->qrec, &e->bhits, &e->bhit_cnt, &e->ambig, &e->skip, &e->mz_cnt, &e->hit_cnt, &e->rep_len, &e->an_cnt, &e->an_off,
 	               &e->n_chain, &e->n_reg, &e->best_mlen, &e->hist_sums, &e->hist_offs, &e->scan_sums, &e->hit_off, &e->a, &e->f, &e->p, &e->v, &e->t, &e->u,
 	               &e->chains_tmp, &e->regs, &e->regx, &e->k64a, &e->k64b, &e->tmp_i32, &e->gated,
-	               &e->hits_csr, &e->stats, &e->cls_count, &e->cls_list };
+	               &e->hits_csr, &e->stats, &e->cls_count, &e->cls_list,
+	               &e->ex_off, &e->ex_alns, &e->ex_coff, &e->ex_csoff, &e->ex_mdoff, &e->ex_sums, &e->ex_cigar, &e->ex_cs, &e->ex_md };
 	for (Buf *b : all) f(b);
 }
 
@@ -585,6 +597,7 @@ extern "C" void mnc_engine_destroy(mnc_engine *e)
 	}
 	if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
 	if (e->ev_lfill) (void)hipEventDestroy(e->ev_lfill);
+	for (int k = 0; k < 2; ++k) if (e->ev_ex[k]) (void)hipEventDestroy(e->ev_ex[k]);
 	if (e->copy_stream) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamDestroy(e->copy_stream); }
 	if (e->ev_prefetch) (void)hipEventDestroy(e->ev_prefetch);
 	if (e->mailbox) (void)hipHostFree(e->mailbox);
@@ -710,7 +723,7 @@ extern "C" int mnc_engine_set_index(mnc_engine *e, mnc_index *idx)
 	DeviceIndex *d = nullptr;
 	if (int rc = index_upload(idx, e->device, &d)) return rc;
 	e->idx = idx, e->didx = d;
-	e->have_batch = false;
+	e->have_batch = false, e->ex_valid = false;
 	return MNC_OK;
 }
 
@@ -1298,7 +1311,7 @@ extern "C" int mnc_classify_device(mnc_engine *e, const uint8_t *d_bases, const 
 	if (wide && n_reads > (uint32_t)WIDE_MAX_READS) { set_error("at most 2^16 reads in a call with reads of 2^20 bases or more (wide query records hold a 16-bit read ordinal)"); return MNC_ERR_UNSUPPORTED; }
 	if (total_bases >= (1LL << 40)) return MNC_ERR_UNSUPPORTED;
 	HIP_TRY(hipSetDevice(e->device));
-	e->have_batch = false, e->last_total_hits = -1, e->have_merged = false, e->cur_wide = wide;
+	e->have_batch = false, e->last_total_hits = -1, e->have_merged = false, e->cur_wide = wide, e->ex_valid = false;
 	// the MAPQ look-ups reach as far as the longest read can score (and exist again after a failed enlargement)
 	const int64_t logf_want = wide ? std::min<int64_t>((int64_t)e->idx->par.a * max_read_len + 1024, INT32_MAX / 8) : 1 << 21;
 	if (logf_want > e->logf_n) {
@@ -1579,6 +1592,132 @@ extern "C" int mnc_engine_fetch_hits(mnc_engine *e, int64_t *hit_offsets, mnc_hi
 	HIP_TRY(hipMemcpyAsync(hit_offsets, d_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
 	if (e->last_total_hits > 0) HIP_TRY(hipMemcpyAsync(hits, e->hits_csr.p, (size_t)e->last_total_hits * sizeof(mnc_hit_t), hipMemcpyDeviceToHost, st));
 	return mnc_engine_sync(e);
+}
+
+// ---------------------------------------------------------------- alignment records of the last batch
+// Records, CSR, CIGAR pool and (on request) the cs / MD pools, built on the engine's stream from what the batch left in
+// HBM (k_export.hip).  Two small read-backs: the record count (it sizes the record pool) and the three pool totals;
+// the pass that fills the pools is left running.
+extern "C" int mnc_engine_export_alignments(mnc_engine *e, int what, int64_t *n_aln, int64_t *n_cigar_words, int64_t *n_cs_bytes, int64_t *n_md_bytes)
+{
+	if (!e || (what & ~(MNC_ALN_CS | MNC_ALN_MD))) return MNC_ERR_ARG;
+	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
+	if (e->have_merged) {
+		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
+		          "alone -- classify the two groups in separate calls to export their alignments");
+		return MNC_ERR_UNSUPPORTED;
+	}
+	const Batch &B = e->B;
+	const size_t nr = B.n_reads;
+	if (what && (nr ? B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("cs / MD exist under MNC_CONTRACT_DP only"); return MNC_ERR_ARG; }
+	HIP_TRY(hipSetDevice(e->device));
+	hipStream_t st = e->stream;
+	e->ex_valid = false, e->ev_ex_used = false;
+	int64_t tot[4] = { 0, 0, 0, 0 };                          // records, CIGAR words, cs bytes, md bytes
+	if (nr) {
+		int rc = e->ex_off.ensure((nr + 2) * 8);
+		if (!rc) rc = e->ex_sums.ensure((nr / SC_TILE + 4) * 8);
+		if (rc) return rc;
+		if (e->profiling) {
+			for (int k = 0; k < 2; ++k) if (!e->ev_ex[k]) HIP_TRY(hipEventCreate(&e->ev_ex[k]));
+			HIP_TRY(hipEventRecord(e->ev_ex[0], st));
+		}
+		int64_t *aln_off = e->ex_off.as<int64_t>();
+		exclusive_scan(ScanInPlain<int32_t>{B.n_reg}, (int64_t)nr, aln_off, e->ex_sums.as<int64_t>(), st);
+		MailList ml;
+		ml.n = 1, ml.it[0] = { aln_off + nr, 0, 2 };
+		hipLaunchKernelGGL(mnc_mail, dim3(1), dim3(64), 0, st, ml, e->mailbox);
+		HIP_TRY(hipStreamSynchronize(st));
+		memcpy(&tot[0], e->mailbox, 8);
+		const size_t na = (size_t)tot[0];
+		if (tot[0] < 0) { set_error("record count %lld out of range", (long long)tot[0]); return MNC_ERR_HIP; }
+		rc = e->ex_alns.ensure((na + 1) * sizeof(mnc_aln_t));
+		if (!rc) rc = e->ex_coff.ensure((na + 2) * 8);
+		if (!rc) rc = e->ex_csoff.ensure((na + 2) * 8);
+		if (!rc) rc = e->ex_mdoff.ensure((na + 2) * 8);
+		if (!rc) rc = e->ex_sums.ensure((na / SC_TILE + 4) * 8);
+		if (rc) return rc;
+		mnc_aln_t *alns = e->ex_alns.as<mnc_aln_t>();
+		int64_t *coff = e->ex_coff.as<int64_t>(), *csoff = e->ex_csoff.as<int64_t>(), *mdoff = e->ex_mdoff.as<int64_t>();
+		launch_export_records(B, aln_off, alns, tot[0], st);
+		if (what) launch_export_strings(B, false, alns, tot[0], coff, csoff, mdoff, nullptr, nullptr, nullptr, what, st);
+		launch_export_scan(alns, tot[0], 0, coff, e->ex_sums.as<int64_t>(), st);
+		if (what & MNC_ALN_CS) launch_export_scan(alns, tot[0], 1, csoff, e->ex_sums.as<int64_t>(), st);
+		if (what & MNC_ALN_MD) launch_export_scan(alns, tot[0], 2, mdoff, e->ex_sums.as<int64_t>(), st);
+		ml.n = 1, ml.it[0] = { coff + na, 0, 2 };
+		if (what & MNC_ALN_CS) ml.it[ml.n++] = { csoff + na, 2, 2 };
+		if (what & MNC_ALN_MD) ml.it[ml.n++] = { mdoff + na, 4, 2 };
+		hipLaunchKernelGGL(mnc_mail, dim3(1), dim3(64), 0, st, ml, e->mailbox);
+		HIP_TRY(hipStreamSynchronize(st));
+		memcpy(&tot[1], e->mailbox, 8);
+		if (what & MNC_ALN_CS) memcpy(&tot[2], e->mailbox + 2, 8);
+		if (what & MNC_ALN_MD) memcpy(&tot[3], e->mailbox + 4, 8);
+		rc = e->ex_cigar.ensure(((size_t)tot[1] + 1) * 4);
+		if (!rc) rc = e->ex_cs.ensure((size_t)tot[2] + 8);
+		if (!rc) rc = e->ex_md.ensure((size_t)tot[3] + 8);
+		if (rc) return rc;
+		launch_export_strings(B, true, alns, tot[0], coff, csoff, mdoff, e->ex_cigar.as<uint32_t>(), e->ex_cs.as<char>(), e->ex_md.as<char>(), what, st);
+		if (e->profiling) { HIP_TRY(hipEventRecord(e->ev_ex[1], st)); e->ev_ex_used = true; }
+		HIP_TRY(hipGetLastError());
+	}
+	e->ex_n_reads = (int64_t)nr, e->ex_n_aln = tot[0], e->ex_n_cig = tot[1], e->ex_n_cs = tot[2], e->ex_n_md = tot[3];
+	e->ex_valid = true;
+	if (n_aln) *n_aln = tot[0];
+	if (n_cigar_words) *n_cigar_words = tot[1];
+	if (n_cs_bytes) *n_cs_bytes = tot[2];
+	if (n_md_bytes) *n_md_bytes = tot[3];
+	return MNC_OK;
+}
+
+extern "C" int mnc_engine_fetch_alignments(mnc_engine *e, int64_t *aln_offsets, mnc_aln_t *alns, int64_t cap_aln, uint32_t *cigar, int64_t cap_cigar,
+                                           char *cs, int64_t cap_cs, char *md, int64_t cap_md)
+{
+	if (!e) return MNC_ERR_ARG;
+	if (!e->ex_valid) { set_error("no alignments have been exported for the last batch"); return MNC_ERR_ARG; }
+	if (cap_aln < e->ex_n_aln || cap_cigar < e->ex_n_cig || cap_cs < e->ex_n_cs || cap_md < e->ex_n_md) {
+		set_error("buffers too small: %lld records, %lld CIGAR words, %lld cs bytes, %lld MD bytes", (long long)e->ex_n_aln, (long long)e->ex_n_cig,
+		          (long long)e->ex_n_cs, (long long)e->ex_n_md);
+		return MNC_ERR_RANGE;
+	}
+	if ((e->ex_n_aln && !alns) || (e->ex_n_cig && !cigar) || (e->ex_n_cs && !cs) || (e->ex_n_md && !md)) return MNC_ERR_ARG;
+	HIP_TRY(hipSetDevice(e->device));
+	hipStream_t st = e->stream;
+	if (aln_offsets) {
+		if (e->ex_n_reads) HIP_TRY(hipMemcpyAsync(aln_offsets, e->ex_off.p, ((size_t)e->ex_n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+		else aln_offsets[0] = 0;
+	}
+	if (e->ex_n_aln) HIP_TRY(hipMemcpyAsync(alns, e->ex_alns.p, (size_t)e->ex_n_aln * sizeof(mnc_aln_t), hipMemcpyDeviceToHost, st));
+	if (e->ex_n_cig) HIP_TRY(hipMemcpyAsync(cigar, e->ex_cigar.p, (size_t)e->ex_n_cig * 4, hipMemcpyDeviceToHost, st));
+	if (e->ex_n_cs) HIP_TRY(hipMemcpyAsync(cs, e->ex_cs.p, (size_t)e->ex_n_cs, hipMemcpyDeviceToHost, st));
+	if (e->ex_n_md) HIP_TRY(hipMemcpyAsync(md, e->ex_md.p, (size_t)e->ex_n_md, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return MNC_OK;
+}
+
+extern "C" int mnc_engine_alignments_device(mnc_engine *e, const int64_t **d_aln_offsets, const mnc_aln_t **d_alns, const uint32_t **d_cigar,
+                                            const char **d_cs, const char **d_md)
+{
+	if (!e) return MNC_ERR_ARG;
+	if (!e->ex_valid) { set_error("no alignments have been exported for the last batch"); return MNC_ERR_ARG; }
+	if (d_aln_offsets) *d_aln_offsets = e->ex_n_reads ? e->ex_off.as<int64_t>() : nullptr;
+	if (d_alns) *d_alns = e->ex_n_aln ? e->ex_alns.as<mnc_aln_t>() : nullptr;
+	if (d_cigar) *d_cigar = e->ex_n_cig ? e->ex_cigar.as<uint32_t>() : nullptr;
+	if (d_cs) *d_cs = e->ex_n_cs ? e->ex_cs.as<char>() : nullptr;
+	if (d_md) *d_md = e->ex_n_md ? e->ex_md.as<char>() : nullptr;
+	return MNC_OK;
+}
+
+extern "C" int mnc_engine_export_ms(mnc_engine *e, double *ms)
+{
+	if (!e || !ms) return MNC_ERR_ARG;
+	*ms = 0;
+	if (!e->ev_ex_used) return MNC_OK;                      // no export since profiling was switched on (or an empty batch)
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(hipEventSynchronize(e->ev_ex[1]));
+	float t = 0;
+	HIP_TRY(hipEventElapsedTime(&t, e->ev_ex[0], e->ev_ex[1]));
+	*ms = t;
+	return MNC_OK;
 }
 
 // ---------------------------------------------------------------- counters / dumps

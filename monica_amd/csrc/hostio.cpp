@@ -1036,6 +1036,53 @@ extern "C" int mnc_fastq_route(const mnc_fastq *fq, const uint8_t *dest, const i
 	return rc;
 }
 
+// ---------------------------------------------------------------- PAF lines of a batch's alignment records
+// One line per record (mnc_engine_fetch_alignments' arrays), appended to `path`: minimap2's 12 columns and the tags of
+// `minimap2 -c` that the records hold; cg / cs / MD for each pool that is given.
+extern "C" int mnc_fastq_write_paf(const mnc_fastq *fq, const mnc_index *idx, const int64_t *aln_offsets, const mnc_aln_t *alns,
+                                   const uint32_t *cigar, const char *cs, const char *md, int flags, const char *path)
+{
+	if (!fq || !idx || !aln_offsets || !path) return MNC_ERR_ARG;
+	if (aln_offsets[fq->n] > aln_offsets[0] && !alns) return MNC_ERR_ARG;
+	try {
+		std::string b;
+		char num[160];
+		for (uint32_t r = 0; r < fq->n; ++r) {
+			const int64_t qlen = fq->offsets[r + 1] - fq->offsets[r];
+			for (int64_t i = aln_offsets[r]; i < aln_offsets[r + 1]; ++i) {
+				const mnc_aln_t &a = alns[i];
+				if ((flags & MNC_PAF_PRIMARY_ONLY) && !(a.flags & 1)) continue;
+				if (a.rid < 0 || a.rid >= (int)idx->contig_name.size()) { set_error("record %lld names contig %d, the index has %zu", (long long)i, a.rid, idx->contig_name.size()); return MNC_ERR_ARG; }
+				b.append(fq->titles.data() + fq->title_off[r] + fq->id_off[r], fq->id_len[r]);
+				snprintf(num, sizeof num, "\t%lld\t%d\t%d\t%c\t", (long long)qlen, a.qs, a.qe, a.rev ? '-' : '+');
+				b += num;
+				b += idx->contig_name[a.rid];
+				snprintf(num, sizeof num, "\t%lld\t%d\t%d\t%d\t%d\t%d\ttp:A:%c\tcm:i:%d\ts1:i:%d\tNM:i:%d\tAS:i:%d\tms:i:%d\tnn:i:%d",
+				         (long long)idx->contig_len[a.rid], a.rs, a.re, a.mlen, a.blen, a.mapq, (a.flags & 1) ? 'P' : 'S', a.cnt, a.score, a.nm,
+				         a.dp_score, a.dp_max, a.n_ambi);
+				b += num;
+				if (cigar) {
+					b += "\tcg:Z:";
+					for (int k = 0; k < a.n_cigar; ++k) {
+						const uint32_t w = cigar[a.cigar_off + k];
+						snprintf(num, sizeof num, "%u%c", w >> 4, (w & 0xf) < 3 ? "MID"[w & 0xf] : '?');
+						b += num;
+					}
+				}
+				if (cs) b += "\tcs:Z:", b.append(cs + a.cs_off, (size_t)a.cs_len);
+				if (md) b += "\tMD:Z:", b.append(md + a.md_off, (size_t)a.md_len);
+				b += '\n';
+			}
+		}
+		FILE *f = fopen(path, "ab");
+		if (!f) { set_error("cannot open %s: %s", path, strerror(errno)); return MNC_ERR_IO; }
+		const bool ok = (b.empty() || fwrite(b.data(), 1, b.size(), f) == b.size()) && fflush(f) == 0;
+		const int cerr = fclose(f);
+		if (!ok || cerr != 0) { set_error("write to %s failed", path); return MNC_ERR_IO; }
+	} catch (const std::bad_alloc &) { set_error("out of host memory (PAF lines)"); return MNC_ERR_NOMEM; }
+	return MNC_OK;
+}
+
 namespace {
 struct HitState { int32_t hits, nm, mlen, name, tied; };
 }

@@ -670,6 +670,25 @@ extern "C" int64_t mnc_index_genome_len(const mnc_index *idx, int gid)
 	return idx && gid >= 0 && gid < (int)idx->genome_len.size() ? idx->genome_len[gid] : -1;
 }
 
+// mappy.Aligner.seq() (mm_idx_getseq): bases [start, end) of a contig from the 4-bit store, as "ACGTN"
+extern "C" int mnc_index_getseq(const mnc_index *idx, int rid, int64_t start, int64_t end, char *out)
+{
+	if (!idx || rid < 0 || rid >= (int)idx->contig_len.size()) { set_error("contig %d out of range", rid); return MNC_ERR_ARG; }
+	if (start < 0 || end < start || end > idx->contig_len[rid]) {
+		set_error("interval [%lld, %lld) outside contig %d of %lld bases", (long long)start, (long long)end, rid, (long long)idx->contig_len[rid]);
+		return MNC_ERR_ARG;
+	}
+	if (end > start && !out) return MNC_ERR_ARG;
+	if ((size_t)rid + 1 >= idx->seq_off.size()) { set_error("the index holds no contig bases"); return MNC_ERR_ARG; }
+	const int64_t base = idx->seq_off[rid];
+	for (int64_t i = start; i < end; ++i) {
+		const int64_t o = base + i;
+		const uint32_t c = idx->seq4[(size_t)(o >> 3)] >> ((o & 7) * 4) & 15u;
+		out[i - start] = "ACGTN"[c < 4 ? c : 4];
+	}
+	return MNC_OK;
+}
+
 extern "C" int mnc_index_dump(const mnc_index *idx, uint64_t *hash, uint64_t *y, int64_t cap, int64_t *n)
 {
 	if (!idx || !n) return MNC_ERR_ARG;

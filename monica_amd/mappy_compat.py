@@ -163,9 +163,28 @@ def _build_device(device):
 class Hit:
     """The attributes of a mappy alignment."""
     __slots__ = ("ctg", "ctg_len", "r_st", "r_en", "q_st", "q_en", "strand", "mapq", "mlen", "blen", "NM",
-                 "is_primary", "score", "n_anchors", "cigar")
+                 "is_primary", "score", "n_anchors", "cigar", "cs", "MD", "trans_strand", "read_num")
+
+    @classmethod
+    def from_record(cls, rec, index, cigar_words, cs=None, md=None):
+        """From one alignment record of `Engine.alignments()` (ALN_DTYPE) and the pools it points into."""
+        h = cls.__new__(cls)
+        rid = int(rec["rid"])
+        h.ctg, h.ctg_len = index.contig_names[rid], index.contig_lens[rid]
+        h.r_st, h.r_en, h.q_st, h.q_en = int(rec["rs"]), int(rec["re"]), int(rec["qs"]), int(rec["qe"])
+        h.strand = -1 if rec["rev"] else 1
+        h.mapq, h.mlen, h.blen, h.NM = int(rec["mapq"]), int(rec["mlen"]), int(rec["blen"]), int(rec["nm"])
+        o, n = int(rec["cigar_off"]), int(rec["n_cigar"])
+        h.cigar = [[int(w) >> 4, int(w) & 0xf] for w in cigar_words[o:o + n]]
+        h.is_primary = bool(int(rec["flags"]) & _capi.ALN_PRIMARY)
+        h.score, h.n_anchors = int(rec["score"]), int(rec["cnt"])
+        h.cs = bytes(cs[int(rec["cs_off"]):int(rec["cs_off"]) + int(rec["cs_len"])]).decode() if cs is not None else ""
+        h.MD = bytes(md[int(rec["md_off"]):int(rec["md_off"]) + int(rec["md_len"])]).decode() if md is not None else ""
+        h.trans_strand, h.read_num = 0, 1
+        return h
 
     def __init__(self, reg, index, cigar=None):
+        self.cs, self.MD, self.trans_strand, self.read_num = "", "", 0, 1      # (mappy: empty unless asked for; unspliced, unpaired)
         rid = int(reg["rid"])
         self.ctg = index.contig_names[rid]
         self.ctg_len = index.contig_lens[rid]
@@ -331,7 +350,76 @@ class Aligner:
         b = seq if isinstance(seq, (bytes, bytearray)) else str(seq).encode()
         eng = self.engine()
         eng.classify(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.int64), 0)
-        regs = eng.dump(_capi.DUMP_REGS, _capi.REG_DTYPE)
-        cigs = eng.cigars()
-        for reg, cig in zip(regs, cigs):
-            yield Hit(reg, self._index, cig)
+        _, recs, cig, cs_b, md_b = eng.alignments(cs=cs, MD=MD)
+        for rec in recs:
+            yield Hit.from_record(rec, self._index, cig, cs_b if cs else None, md_b if MD else None)
+
+    def map_batch_alignments(self, bases, offsets, cs=False, MD=False, min_mapq=0):
+        """Everything `map()` yields, for a whole batch in one go: (aln_offsets[n + 1], records (`_capi.ALN_DTYPE`), cigar
+        words, cs bytes, md bytes) -- `Engine.alignments()` of the batch; `min_mapq` only sets the records' gate bit.  The
+        engine holds one pass: with long reads on, a batch that mixes reads of 2^20 bases or more with shorter ones is
+        classified as two calls here and the two sets of records are merged by read ordinal."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        eng = self.engine()
+        lens = np.diff(offsets)
+        long_ = lens > _capi.MAX_READ_LEN
+        if not self._long_reads or not long_.any() or long_.all():
+            eng.classify(bases, offsets, min_mapq)
+            return eng.alignments(cs=cs, MD=MD)
+        parts = []
+        for sel in (np.flatnonzero(~long_), np.flatnonzero(long_)):
+            sub_b, sub_o = _take_reads(bases, offsets, sel)
+            eng.classify(sub_b, sub_o, min_mapq)
+            parts.append((sel,) + eng.alignments(cs=cs, MD=MD))
+        return _merge_alignments(n, parts)
+
+    def seq(self, name, start=0, end=0x7fffffff):
+        """mappy's `Aligner.seq`: bases [start, end) of contig `name` (end clipped to the contig), None for an unknown
+        name or an empty / inverted interval."""
+        if self._index is None:
+            return None
+        try:
+            rid = self._index.contig_names.index(name)
+        except ValueError:
+            return None
+        end = min(int(end), self._index.contig_lens[rid])
+        if start < 0 or start >= end:
+            return None
+        return self._index.getseq(rid, int(start), end).decode()
+
+
+def _take_reads(bases, offsets, sel):
+    """The reads `sel` (ordinals) of a batch as a batch of their own."""
+    out_o = np.zeros(len(sel) + 1, dtype=np.int64)
+    np.cumsum(offsets[sel + 1] - offsets[sel], out=out_o[1:])
+    out_b = np.concatenate([bases[offsets[r]:offsets[r + 1]] for r in sel]) if out_o[-1] else np.zeros(0, dtype=np.uint8)
+    return out_b, out_o
+
+
+def _merge_alignments(n, parts):
+    """Records of several calls over disjoint reads of one batch -> one set in read order.  parts: (read ordinals of the
+    call, offsets, records, cigar, cs, md); pool offsets and `read` are rewritten for the merged pools."""
+    owner = np.zeros(n, dtype=np.int64)
+    local = np.zeros(n, dtype=np.int64)
+    for k, part in enumerate(parts):
+        owner[part[0]], local[part[0]] = k, np.arange(len(part[0]))
+    offs = np.zeros(n + 1, dtype=np.int64)
+    recs, pools = [], [[], [], []]
+    fill = [0, 0, 0]
+    for r in range(n):
+        _, off, rec, cig, cs_b, md_b = parts[owner[r]]
+        lo, hi = off[local[r]], off[local[r] + 1]
+        for a in rec[lo:hi]:
+            a = a.copy()
+            a["read"] = r
+            for j, (src, o_key, n_key) in enumerate(((cig, "cigar_off", "n_cigar"), (cs_b, "cs_off", "cs_len"), (md_b, "md_off", "md_len"))):
+                pools[j].append(src[a[o_key]:a[o_key] + a[n_key]])
+                a[o_key] = fill[j]
+                fill[j] += int(a[n_key])
+            recs.append(a)
+        offs[r + 1] = len(recs)
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt, copy=False) if xs else np.zeros(0, dtype=dt)
+    records = np.array(recs, dtype=_capi.ALN_DTYPE) if recs else np.zeros(0, dtype=_capi.ALN_DTYPE)
+    return offs, records, cat(pools[0], np.uint32), cat(pools[1], np.uint8), cat(pools[2], np.uint8)
