@@ -176,6 +176,12 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *                                                are all long exports like any other
  *   cs / MD under MNC_CONTRACT_CHAIN             mnc_engine_export_alignments: MNC_ERR_ARG (no base-level alignment: records
  *                                                only, n_cigar = 0)
+ *   coverage after a call that ran both the      mnc_engine_add_coverage: MNC_ERR_UNSUPPORTED, the accumulator untouched (the
+ *   usual and the wide pass                      engine holds the wide pass alone); classify the two groups in separate calls
+ *   coverage without MNC_COV_SPAN under          mnc_engine_add_coverage: MNC_ERR_ARG (no CIGAR to take the M columns from)
+ *   MNC_CONTRACT_CHAIN
+ *   a reference base overlapped by 2^31 or more  outside the contract: the depth track holds int32 (mnc_coverage_reset
+ *   added records                                starts over)
  */
 
 /* ---------------------------------------------------------------- classify
@@ -388,6 +394,75 @@ int mnc_engine_export_ms(mnc_engine *eng, double *ms);
 /* mappy.Aligner.seq(): bases [start, end) of contig rid as "ACGTN" (not NUL-terminated); MNC_ERR_ARG when rid or the
  * interval is out of range (0 <= start <= end <= contig length) */
 int mnc_index_getseq(const mnc_index *idx, int rid, int64_t start, int64_t end, char *out /* end-start bytes, "ACGTN" */);
+
+/* ---------------------------------------------------------------- coverage
+ * Where on the genomes the reads landed: depth and breadth of coverage per contig, accumulated on the device from batch
+ * to batch the way mnc_classify_device's d_counts is.  The reference counts per genome in three modes (aligner.py:247-263:
+ * 'basic', 'query_length', 'matching'); this is a fourth kind of count over the same hits -- per reference base instead of
+ * per genome -- made from the regions and region CIGARs of the last batch as they stand in HBM (csrc/k_coverage.hip).  A
+ * batch that does not ask for it costs not one more kernel, allocation or byte.
+ *
+ * An mnc_coverage belongs to one index on one device and holds a depth track over every reference base of that index.  It
+ * is additive: adding batch A and then batch B equals adding one batch with the reads of both; it lives across any number
+ * of classify calls and across engines of the same index and device.  One thread at a time, like an engine.
+ *
+ * What a call adds -- `what` = exactly ONE selector, optionally | MNC_COV_SPAN:
+ *   MNC_COV_GATED     every record that passes the gate of the call (primary and mapq >= min_mapq: mnc_aln_t.flags bit 1)
+ *   MNC_COV_PRIMARY   every primary record (flags bit 0)
+ *   MNC_COV_ALL       every record: secondaries, Z-drop splits and inversion regions alike
+ *   MNC_COV_ASSIGNED  for each read whose decision in THIS call is a contig (out_assign >= 0), the one gated record that
+ *                     best_hit chose (aligner.py:328-339): the gated record with the smallest nm / mlen by int64
+ *                     cross-products as in mnc_best_hit -- unique whenever the decision is a contig, since best_hit answers
+ *                     ambiguous exactly when its last update was a tie.  Reads that come back unmapped, ambiguous or
+ *                     skipped add nothing.  Across the parts of a multi-part database the final decision is known only
+ *                     after the last part (aligner.py:196-203, 218-223): a caller there adds MNC_COV_GATED per part.
+ *                     After mnc_classify_device the caller's d_assign must still be there.
+ *   default           a record adds 1 to the depth of every reference base in its M columns; reference bases under a D are
+ *                     not covered (as in `samtools depth`); insertions consume no reference
+ *   MNC_COV_SPAN      a record adds 1 to every base of [rs, re) whatever its CIGAR.  Under MNC_CONTRACT_CHAIN there is no
+ *                     CIGAR and SPAN is required: a call without it is MNC_ERR_ARG (the rule of cs / MD)
+ * After a call that ran both the usual and the wide pass the engine holds the wide pass alone: MNC_ERR_UNSUPPORTED and the
+ * accumulator untouched, as mnc_engine_export_alignments; a call whose reads are all long adds like any other. */
+typedef struct mnc_coverage mnc_coverage;
+#define MNC_COV_GATED    1
+#define MNC_COV_PRIMARY  2
+#define MNC_COV_ALL      4
+#define MNC_COV_ASSIGNED 8
+#define MNC_COV_SPAN     16
+/* aligner.py:247-263 (a Counter per sample; here a track per index and device).  bin_bases >= 1: the width of the bins of
+ * the per-contig profile (mnc_coverage_fetch_bins); bins do not cross contigs, the last bin of a contig is short.
+ * MNC_ERR_ARG for bin_bases < 1, MNC_ERR_NODEVICE without a gfx950 device, MNC_ERR_NOMEM when HBM is short. */
+int  mnc_coverage_create(mnc_index *idx, int device, int bin_bases, mnc_coverage **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_coverage_free(mnc_coverage *cov);
+/* clears the depth track and the alignment counts (`Counter()` anew, aligner.py:247); asynchronous */
+int  mnc_coverage_reset(mnc_coverage *cov);
+/* HBM the accumulator holds: 4 bytes per reference base, a few words per contig and 8 bytes per 1 024 bases of scratch */
+int  mnc_coverage_device_bytes(const mnc_coverage *cov, int64_t *bytes);
+/* aligner.py:247-263, the fourth kind: adds the last classified batch of `eng` as it stands in HBM.  Needs no
+ * mnc_engine_export_alignments and disturbs none made before or after.  Asynchronous on the engine's stream, no host wait.
+ * MNC_ERR_ARG: `cov` is for another index or device than the engine's current ones; no selector or more than one; no
+ * batch has been classified yet; no MNC_COV_SPAN under MNC_CONTRACT_CHAIN.  The accumulator is untouched on any error. */
+int  mnc_engine_add_coverage(mnc_engine *eng, mnc_coverage *cov, int what);
+/* aligner.py:247-263 read out: one value per contig, any pointer may be NULL.  covered = bases with depth > 0;
+ * depth_sum = the sum of depth over the contig's bases; max_depth; n_aln = records added to the contig.  Waits for the
+ * work queued so far and leaves the accumulator as it is: it can be called between the batches of a run. */
+int  mnc_coverage_summary(mnc_coverage *cov, int64_t *covered, int64_t *depth_sum, int32_t *max_depth, int64_t *n_aln);
+/* the profile of one contig: covered bases and depth sum per bin of bin_bases bases.  *n_bins = ceil(len / bin_bases);
+ * MNC_ERR_RANGE, with *n_bins set and nothing written, when cap is short; MNC_ERR_ARG for a bad rid.  Either array may be
+ * NULL. */
+int  mnc_coverage_fetch_bins(mnc_coverage *cov, int rid, int32_t *bin_covered, int64_t *bin_depth_sum, int64_t cap, int64_t *n_bins);
+/* per-base depth of bases [start, end) of contig rid; the interval is checked as by mnc_index_getseq (MNC_ERR_ARG).  For
+ * tests and zoomed plots: the contig's track is summed from its first base up to `end`. */
+int  mnc_coverage_fetch_depth(mnc_coverage *cov, int rid, int64_t start, int64_t end, int32_t *depth /* end - start */);
+/* The raw additive track (device pointer), for ranks that sum their tracks with a collective of their own (int32 sum over
+ * n_words words, e.g. ncclAllReduce; none is added here).  Layout: n_words = total_len int32 words, the contigs back to
+ * back in index order without padding -- base p of contig c is word (sum of the lengths of contigs 0 .. c - 1) + p -- holding
+ * depth DIFFERENCES: +1 where a covered run starts, -1 one past where it ends; depth(c, p) = the sum of contig c's words
+ * 0 .. p, starting anew at every contig.  The -1 of a run that ends on a contig's last base would fall on the next contig's
+ * first word and is dropped, so a contig's words need not sum to zero.  Ordered behind the adds only after
+ * mnc_coverage_summary or a sync of the engines that added. */
+int  mnc_coverage_device(mnc_coverage *cov, const int32_t **d_track, int64_t *n_words);
 
 /* ---------------------------------------------------------------- FASTQ batches and read routing
  * Replaces the per-record Biopython objects of the reference's loop:

@@ -38,6 +38,10 @@ assert ALN_DTYPE.itemsize == 104
 ALN_CS, ALN_MD = 1, 2
 ALN_PRIMARY, ALN_GATED = 1, 2           # mnc_aln_t.flags bits 0 / 1; bits 8.. are mnc_reg_t.flags << 8
 PAF_PRIMARY_ONLY = 1
+# MNC_COV_*: what Engine.add_coverage adds -- exactly one selector, optionally | COV_SPAN
+COV_GATED, COV_PRIMARY, COV_ALL, COV_ASSIGNED, COV_SPAN = 1, 2, 4, 8, 16
+# one row per contig of Coverage.summary()
+COV_SUMMARY_DTYPE = np.dtype([("covered", "<i8"), ("depth_sum", "<i8"), ("max_depth", "<i4"), ("n_aln", "<i8")])
 MZ_DTYPE = np.dtype([("hash", "<u4"), ("pos_strand", "<u4")])
 ANCHOR_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8")])
 
@@ -74,6 +78,8 @@ EXPORTS = [
     "mnc_synth_genome", "mnc_synth_diverge", "mnc_synth_reads", "mnc_synth_reads_device", "mnc_version",
     "mnc_engine_export_alignments", "mnc_engine_fetch_alignments", "mnc_engine_alignments_device", "mnc_engine_export_ms",
     "mnc_index_getseq", "mnc_fastq_write_paf",
+    "mnc_coverage_create", "mnc_coverage_free", "mnc_coverage_reset", "mnc_coverage_device_bytes", "mnc_engine_add_coverage",
+    "mnc_coverage_summary", "mnc_coverage_fetch_bins", "mnc_coverage_fetch_depth", "mnc_coverage_device",
 ]
 
 
@@ -205,6 +211,15 @@ def lib():
     sig("mnc_engine_export_ms", i32, [vp, C.POINTER(C.c_double)])
     sig("mnc_index_getseq", i32, [vp, i32, i64, i64, vp])
     sig("mnc_fastq_write_paf", i32, [vp, vp, vp, vp, vp, vp, vp, i32, cp])
+    sig("mnc_coverage_create", i32, [vp, i32, i32, pp])
+    sig("mnc_coverage_free", None, [vp])
+    sig("mnc_coverage_reset", i32, [vp])
+    sig("mnc_coverage_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_engine_add_coverage", i32, [vp, vp, i32])
+    sig("mnc_coverage_summary", i32, [vp, vp, vp, vp, vp])
+    sig("mnc_coverage_fetch_bins", i32, [vp, i32, vp, vp, i64, C.POINTER(i64)])
+    sig("mnc_coverage_fetch_depth", i32, [vp, i32, i64, i64, vp])
+    sig("mnc_coverage_device", i32, [vp, pp, C.POINTER(i64)])
     _LIB = L
     return L
 
@@ -532,6 +547,11 @@ class Engine:
         check(lib().mnc_engine_export_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
+    def add_coverage(self, cov, what=COV_ASSIGNED):
+        """`mnc_engine_add_coverage`: add the last classified batch, as it stands in HBM, to the accumulator `cov`.
+        `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED, optionally | COV_SPAN.  Asynchronous."""
+        check(lib().mnc_engine_add_coverage(self._h, cov._h if cov is not None else None, int(what)))
+
     def set_profiling(self, on=True):
         check(lib().mnc_engine_set_profiling(self._h, 1 if on else 0))
 
@@ -594,6 +614,74 @@ class Engine:
         buf = np.zeros(max(n.value, 1), dtype=np.uint8)
         check(lib().mnc_engine_dump(self._h, what, buf.ctypes.data, len(buf), C.byref(n)))
         return buf[:n.value].view(dtype).copy()
+
+
+# ---------------------------------------------------------------------------------- coverage
+class Coverage:
+    """Owner of an ``mnc_coverage``: depth of coverage over every reference base of one index on one device, accumulated
+    from batch to batch by `Engine.add_coverage` (include/monica_amd.h, "coverage")."""
+
+    def __init__(self, index, device=0, bin_bases=1024):
+        self.index = index
+        self.device = device
+        self.bin_bases = int(bin_bases)
+        h = C.c_void_p()
+        check(lib().mnc_coverage_create(index._h if index is not None else None, int(device), self.bin_bases, C.byref(h)))
+        self._h = h
+
+    def reset(self):
+        check(lib().mnc_coverage_reset(self._h))
+
+    def device_bytes(self):
+        n = C.c_int64(0)
+        check(lib().mnc_coverage_device_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    def summary(self):
+        """One row per contig (COV_SUMMARY_DTYPE): covered bases, depth sum, maximal depth, records added.  Waits for the
+        adds queued so far; the accumulator stays as it is."""
+        n = len(self.index.contig_lens)
+        cov, dsum, nal = (np.zeros(n, dtype=np.int64) for _ in range(3))
+        mx = np.zeros(n, dtype=np.int32)
+        check(lib().mnc_coverage_summary(self._h, cov.ctypes.data, dsum.ctypes.data, mx.ctypes.data, nal.ctypes.data))
+        out = np.zeros(n, dtype=COV_SUMMARY_DTYPE)
+        out["covered"], out["depth_sum"], out["max_depth"], out["n_aln"] = cov, dsum, mx, nal
+        return out
+
+    def bins(self, rid):
+        """The profile of contig `rid`: (covered bases int32[n_bins], depth sum int64[n_bins]) per bin of `bin_bases`."""
+        n = C.c_int64(0)
+        rc = lib().mnc_coverage_fetch_bins(self._h, int(rid), None, None, 0, C.byref(n))
+        if rc not in (OK, ERR_RANGE):
+            check(rc)
+        cov = np.zeros(n.value, dtype=np.int32)
+        dsum = np.zeros(n.value, dtype=np.int64)
+        check(lib().mnc_coverage_fetch_bins(self._h, int(rid), cov.ctypes.data, dsum.ctypes.data, len(cov), C.byref(n)))
+        return cov, dsum
+
+    def depth(self, rid, start=0, end=None):
+        """Per-base depth of bases [start, end) of contig `rid` (int32)."""
+        end = (self.index.contig_lens[rid] if 0 <= rid < len(self.index.contig_lens) else 0) if end is None else int(end)
+        out = np.zeros(max(end - int(start), 0), dtype=np.int32)
+        check(lib().mnc_coverage_fetch_depth(self._h, int(rid), int(start), end, out.ctypes.data if len(out) else None))
+        return out
+
+    def device_track(self):
+        """(device address of the raw difference track, words): `mnc_coverage_device`."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        check(lib().mnc_coverage_device(self._h, C.byref(p), C.byref(n)))
+        return int(p.value or 0), int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mnc_coverage_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------------------------- host helpers

@@ -64,6 +64,8 @@ BATCH_READS = int(os.environ.get("MONICA_AMD_BATCH_READS", "12500"))
 BATCH_BASES = min(1 << 27, BATCH_READS * 6000)
 # the first batches of a file, as fractions of BATCH_READS: the stages behind the parser wait for the first batch, so it is small
 BATCH_RAMP = tuple(float(x) for x in os.environ.get("MONICA_AMD_BATCH_RAMP", "0.25").split(",") if x.strip())
+COVERAGE_BIN_BASES = 1024         # `coverage=True`: the bin width of the sample's accumulator
+COVERAGE_CSV_HEADER = ("genome", "contig", "length", "covered_bases", "breadth", "mean_depth", "alignments")
 DEFAULT_MAX_WORKERS = int(os.environ.get("MONICA_AMD_MAX_WORKERS", "8"))   # `n_threads=None`: at most this many samples in flight
 TIMINGS = {}                      # per sample name: seconds spent per phase of aligner() (diagnostics)
 PIPE_TRACE = [] if os.environ.get("MONICA_AMD_PIPE_TRACE") else None   # (stage, reads, start, end) per batch and stage (diagnostics)
@@ -122,9 +124,10 @@ def index_loader(index_file):
 def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quality=60, overnight=False, n_threads=None,
                            focus_species=[], output_folder=None, mapped_files_folder=MAPPED_FILES_FOLDER,
                            unmapped_files_folder=UNMAPPED_FILES_FOLDER, ambiguous_files_folder=AMBIGUOUS_FILES_FOLDER,
-                           hits_files_folder=HITS_FILES_FOLDER, focus_file_folder=FOCUS_FILES_FOLDER):
+                           hits_files_folder=HITS_FILES_FOLDER, focus_file_folder=FOCUS_FILES_FOLDER, coverage=None):
     """Classify every non-empty `*fastq` file of `query_folder` against the index parts
-    (aligner.py:65-111): every part but the last only collects hits; the last part decides."""
+    (aligner.py:65-111): every part but the last only collects hits; the last part decides.
+    `coverage` (not in the reference; off by default): see `aligner_coverage`."""
     os.chdir(query_folder)
     samples = [f for f in os.listdir(".") if f.endswith("fastq") and os.stat(f).st_size]
     if not samples:
@@ -154,14 +157,16 @@ def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quali
     try:
         for part in indexes_paths[:-1]:
             index = index_loader(part)
-            pool.starmap(aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
-                                      rep(mapping_quality)))
+            pool.starmap(aligner_coverage if coverage else aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
+                                      rep(mapping_quality), *([rep(False), rep([]), rep(None), rep(None), rep(None), rep(None),
+                                                               rep(False), rep(coverage)] if coverage else [])))
         index = index_loader(indexes_paths[-1])
         _trace("loaded", 0, time.perf_counter())
-        results = pool.starmap(aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
+        results = pool.starmap(aligner_coverage if coverage else aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
                                             rep(mapping_quality), rep(overnight), rep(focus_species),
                                             rep(folders["mapped"]), rep(folders["unmapped"]),
-                                            rep(folders["ambiguous"]), rep(folders["focus"]), rep(True)))
+                                            rep(folders["ambiguous"]), rep(folders["focus"]), rep(True),
+                                            *([rep(coverage)] if coverage else [])))
     finally:
         _trace("mapped", 0, time.perf_counter())
         pool.close()
@@ -176,7 +181,27 @@ def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quali
 def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_quality=None, overnight=False,
             focus_species=[], mapped_folder=None, unmapped_folder=None, ambiguous_folder=None, focus_folder=None,
             last_index=False):
-    """One sample file against one index part (aligner.py:179-279).
+    """One sample file against one index part (aligner.py:179-279), with the reference's signature: `aligner_coverage`
+    with coverage off."""
+    return aligner_coverage(sample, sample_name, index, mode, hits_folder, mapping_quality, overnight, focus_species,
+                            mapped_folder, unmapped_folder, ambiguous_folder, focus_folder, last_index, coverage=None)
+
+
+def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, mapping_quality=None, overnight=False,
+                     focus_species=[], mapped_folder=None, unmapped_folder=None, ambiguous_folder=None, focus_folder=None,
+                     last_index=False, coverage=None):
+    """One sample file against one index part (aligner.py:179-279): `aligner` and the opt-in `coverage=` argument, which
+    the reference does not have (`aligner` itself keeps the reference's parameter list; `multi_threaded_aligner(...,
+    coverage=)` calls this one).
+
+    `coverage` (None / False: off, and nothing changes -- same outputs, same files): True, or the
+    bin width in bases, makes a device accumulator for this sample and index part (`mappy_compat.Aligner.coverage`),
+    adds every batch to it and leaves `<sample_name>.coverage.csv` (`COVERAGE_CSV_HEADER`, one row per contig, appended
+    to) beside the routed files -- in `hits_folder` for a part that routes nothing.  What is added: with one index part
+    the record of every read's decision (`COV_ASSIGNED`); for a database of several parts a read's final decision is
+    known only after the last part, so coverage is collected with `COV_GATED` per part -- every record that passes the
+    gate, in every part's own rows.  A batch that mixes reads of 2^20 bases or more with shorter ones (long reads on)
+    cannot be added (include/monica_amd.h, "limits") and is reported.  The return value is as ever.
 
     Per batch: the library parses the FASTQ records (`mnc_fastq_next`), the GPU classifies them
     (`mnc_classify_batch`), the per-id hit lists carried over from earlier index parts are
@@ -195,6 +220,10 @@ def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_qua
     t_open = time.perf_counter()
     reader = _capi.FastqReader(sample)
     t_open = time.perf_counter() - t_open
+    cov = None
+    if coverage:
+        cov = index.coverage(COVERAGE_BIN_BASES if coverage is True else int(coverage))
+        cov_what = _capi.COV_ASSIGNED if last_index and not os.path.exists(carried_file) else _capi.COV_GATED
 
     clock = TIMINGS.setdefault(sample_name, dict.fromkeys(("parse", "classify", "carry", "route", "count", "engine", "open", "close", "remove"), 0.0))
     clock["engine"] += t_engine
@@ -298,6 +327,13 @@ def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_qua
                 raise
             mappy.release_idle(index.index)
             out = engine.classify_ptr(batch.bases_ptr, batch.offsets_ptr, batch.n, mapping_quality)
+        if cov is not None:
+            try:
+                engine.add_coverage(cov, cov_what)            # asynchronous, behind the batch's kernels
+            except _capi.MncError as err:
+                if err.code != _capi.ERR_UNSUPPORTED:
+                    raise
+                print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no coverage")
         clock["classify"] += time.perf_counter() - t1
         _trace("classify", batch.n, t1)
         n_skipped = int((out[0] == _capi.SKIPPED).sum())
@@ -438,6 +474,12 @@ def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_qua
         reader.close()
         clock["close"] += time.perf_counter() - t0
     _trace("closed", 0, time.perf_counter())
+    if cov is not None:
+        try:
+            if not post_error:
+                write_coverage_csv(cov, os.path.join(mapped_folder if last_index else hits_folder, sample_name + ".coverage.csv"))
+        finally:
+            cov.close()
     if post_error:
         raise post_error[0]
     if not last_index:
@@ -459,6 +501,22 @@ def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_qua
     threading.Thread(target=sample_hits.close, name="mnc-hits-free").start()
     _trace("return", 0, time.perf_counter())
     return sample_alignment, sample_name
+
+
+def write_coverage_csv(cov, path):
+    """One row per contig of the accumulator's index, appended to `path` (the header when the file is new)."""
+    index = cov.index
+    summary = cov.summary()
+    new = not os.path.exists(path) or not os.path.getsize(path)
+    with open(path, "a") as out:
+        if new:
+            out.write(",".join(COVERAGE_CSV_HEADER) + "\n")
+        for rid, row in enumerate(summary):
+            length = int(index.contig_lens[rid])
+            covered, depth_sum = int(row["covered"]), int(row["depth_sum"])
+            out.write("{},{},{},{},{:.6f},{:.6f},{}\n".format(
+                index.genome_names[int(index.contig_genome[rid])], index.contig_names[rid], length, covered,
+                covered / length if length else 0.0, depth_sum / length if length else 0.0, int(row["n_aln"])))
 
 
 def _remove_consumed(sample):

@@ -96,6 +96,10 @@ void launch_export_records(const Batch &B, const int64_t *aln_off, mnc_aln_t *al
 void launch_export_scan(const mnc_aln_t *alns, int64_t n_aln, int field, int64_t *out, int64_t *sums, hipStream_t st);
 void launch_export_strings(const Batch &B, bool write, mnc_aln_t *alns, int64_t n_aln, const int64_t *cig_off, const int64_t *cs_off,
                            const int64_t *md_off, uint32_t *cigar, char *cs, char *md, int what, hipStream_t st);
+// coverage accumulator (k_coverage.hip)
+const mnc_index *coverage_index(const mnc_coverage *cv);
+int coverage_device_of(const mnc_coverage *cv);
+int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream_t st);
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
@@ -193,7 +197,7 @@ static SharedWs *shared_ws(int device, int add_ref)
 }
 
 // ================================================================ index residency
-static int check_device(int device)
+int check_device(int device)                                // (k_coverage.hip uses it as well)
 {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible"); return MNC_ERR_NODEVICE; }
@@ -1718,6 +1722,30 @@ extern "C" int mnc_engine_export_ms(mnc_engine *e, double *ms)
 	HIP_TRY(hipEventElapsedTime(&t, e->ev_ex[0], e->ev_ex[1]));
 	*ms = t;
 	return MNC_OK;
+}
+
+// ---------------------------------------------------------------- coverage of the last batch
+// Adds the batch as it stands in HBM (regions, region CIGARs, decisions) to an accumulator (k_coverage.hip): one kernel on
+// the engine's stream, no read-back.  Every check comes before the launch, so an error leaves the accumulator as it was.
+extern "C" int mnc_engine_add_coverage(mnc_engine *e, mnc_coverage *cov, int what)
+{
+	if (!e || !cov) return MNC_ERR_ARG;
+	const int sel = what & (MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED);
+	if (what & ~(MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED | MNC_COV_SPAN)) { set_error("unknown bits in `what` (0x%x)", what); return MNC_ERR_ARG; }
+	if (sel == 0 || (sel & (sel - 1))) { set_error("exactly one of MNC_COV_GATED / PRIMARY / ALL / ASSIGNED is required"); return MNC_ERR_ARG; }
+	if (coverage_index(cov) != e->idx || coverage_device_of(cov) != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
+	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
+	if (e->have_merged) {
+		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
+		          "alone -- classify the two groups in separate calls to add their coverage");
+		return MNC_ERR_UNSUPPORTED;
+	}
+	const Batch &B = e->B;
+	const bool span = (what & MNC_COV_SPAN) != 0;
+	if (!span && (B.n_reads ? B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("MNC_COV_SPAN is required under MNC_CONTRACT_CHAIN (no CIGAR)"); return MNC_ERR_ARG; }
+	if (B.n_reads == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return coverage_add(cov, B, sel, span, e->stream);
 }
 
 // ---------------------------------------------------------------- counters / dumps

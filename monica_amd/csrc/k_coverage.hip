@@ -1,0 +1,495 @@
+// Depth and breadth of coverage per contig (include/monica_amd.h, "coverage"): an accumulator that lives across classify
+// calls, added to from the last batch as it stands in HBM (regions, region CIGARs).  Runs only when asked for; nothing here
+// is on the classification path.
+//
+// The track.  One int32 per reference base of the index, the contigs back to back without padding: base p of contig c
+// is word off[c] + p, off = the prefix sums of the contig lengths.  It holds DIFFERENCES of depth: a covered run [s, e)
+// adds +1 at s and -1 at e, so a run costs two atomics whatever its length and tracks of several ranks add up word by word.
+// Depth of base p is the sum of the contig's words 0 .. p.
+//   THE CONTIG-END RULE.  A run that ends on the last base of its contig has its -1 one past the contig -- on the first
+//   base of the next one, where it would take one off that contig's depth.  That -1 is DROPPED (cov_put), not stored in a
+//   slot of its own: depth is defined as a sum that starts anew at every contig, so nothing ever reads what lies beyond a
+//   contig's last word, and the track stays at exactly 4 bytes per base in the layout a caller's collective expects.
+//   Consequence: the words of a contig do not sum to zero, and the summary must not let one contig's sum run into the next.
+//
+//   mnc_cov_add_runs   one wave per READ (not per record: a read's live region slots are found as k_export.hip finds them,
+//                      reg_slot(r) .. + n_reg[r], which needs no scan over the batch, no record list and no host wait; a
+//                      read has a handful of records).  Every lane walks the read's records -- the selection is decided
+//                      on the way, for MNC_COV_ASSIGNED by best_hit's int64 cross-products over the gated records -- and
+//                      the wave walks a selected record's CIGAR 64 operations at a time: reference offsets by a prefix
+//                      sum of the reference-consuming lengths, one ballot each of the M and the D operations.  A covered
+//                      run is a maximal stretch of M columns without a D (insertions consume no reference and do not break
+//                      it): the M lane whose nearest M / D neighbour below is a D (or none, with no run carried in) opens
+//                      it, the D lane whose nearest neighbour below is an M closes it at its own start.  Whether a run is
+//                      open across a chunk border is one carried scalar; lane 0 closes the last run after the loop.
+//   mnc_cov_add_span   one lane per read: +1 at rs, -1 at re of every selected record (MNC_COV_SPAN)
+//   mnc_cov_scan       the summary.  Restarting the sum at every contig needs no segmented operator: with G the plain
+//                      running sum of the whole track, depth(c, p) = G(off[c] + p) - G(off[c] - 1), so scan.h's tile sums
+//                      serve as they are, mnc_cov_contig_base finds every contig's G(off[c] - 1), and the pass over the
+//                      tiles subtracts it.  The reductions (covered bases, depth sum, maximum; per bin for one contig's
+//                      profile) are taken in that pass from registers: per-base depth is never stored, the track is only
+//                      read.  A tile inside one contig -- all but a few -- reduces across its workgroup and issues three
+//                      atomics; a tile that spans a contig border lets every lane flush its own.
+#include <hip/hip_runtime.h>
+#include <new>
+#include <vector>
+#include "device.h"
+#include "scan.h"
+
+using namespace mnc;
+
+#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
+	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+	return e_ == hipErrorOutOfMemory ? MNC_ERR_NOMEM : MNC_ERR_HIP; } } while (0)
+
+struct mnc_coverage {
+	mnc_index *idx = nullptr;
+	int device = 0, bin_bases = 0, n_contigs = 0;
+	int64_t n_words = 0;                       // = the index's total_len
+	std::vector<int64_t> off;                  // n_contigs + 1
+	int32_t *track = nullptr;                  // [n_words] depth differences
+	unsigned long long *n_aln = nullptr;       // [n_contigs] records added
+	int64_t *d_off = nullptr;                  // [n_contigs + 1]
+	int64_t *tile_sums = nullptr;              // [n_words / SC_TILE + 2] scratch of the summary
+	long long *cbase = nullptr;                // [n_contigs] running sum of the track before the contig (scratch)
+	unsigned long long *c_cov = nullptr, *c_sum = nullptr;   // [n_contigs] each: the summary's results
+	int32_t *c_max = nullptr;
+	int64_t bytes = 0;
+	// adds run on the engines' streams; reset and the summaries on this one.  ev_add: the last add (this stream waits
+	// for it); ev_own: the last reset / summary (an add waits for it)
+	hipStream_t st = nullptr;
+	hipEvent_t ev_add = nullptr, ev_own = nullptr;
+};
+
+namespace mnc {
+
+int check_device(int device);                  // engine.hip
+
+__device__ __forceinline__ int cov_incl_add(int x)
+{
+	const int lane = lane_id();
+	for (int d = 1; d < 64; d <<= 1) {
+		const int o = __shfl_up(x, d);
+		if (lane >= d) x += o;
+	}
+	return x;
+}
+
+// one end of a run at base `pos` of a contig of `len` bases whose first word is `w`: without a return value.  An end
+// at `len` is the -1 of a run that reaches the contig's last base -- dropped (the contig-end rule above); nothing is
+// ever written outside the contig's own words.
+__device__ __forceinline__ void cov_put(int32_t *w, int64_t len, int64_t pos, int v)
+{
+	if (pos >= 0 && pos < len) (void)__hip_atomic_fetch_add(w + pos, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ bool cov_selected(const mnc_reg_t &r, int sel, int min_mapq)
+{
+	const bool primary = r.id == r.parent;
+	return sel == MNC_COV_ALL || (sel == MNC_COV_PRIMARY && primary) || (primary && r.mapq >= min_mapq);   // GATED, and ASSIGNED's candidates
+}
+
+// MNC_COV_ASSIGNED: the record best_hit chose among the gated ones of a read whose decision is a contig -- the running
+// minimum of NM / mlen by int64 cross-products, as gate_and_decide (k_post.hip) and mnc_best_hit keep it; -1: none
+__device__ __forceinline__ int cov_pick(const Batch &B, uint32_t rd, int64_t slot0, int n)
+{
+	if (B.assign[rd] < 0) return -1;
+	int pick = -1;
+	long long b_nm = 0, b_mlen = 1;
+	for (int i = 0; i < n; ++i) {
+		const mnc_reg_t &x = B.regs[slot0 + i];
+		if (x.id != x.parent || x.mapq < B.min_mapq) continue;
+		const long long nm = x.blen - x.mlen + x.n_ambi, mlen = x.mlen;
+		if (pick < 0 || nm * b_mlen <= b_nm * mlen) pick = i, b_nm = nm, b_mlen = mlen;
+	}
+	return pick;
+}
+
+__global__ __launch_bounds__(256) void mnc_cov_add_runs(Batch B, int sel, const int64_t *off, int n_contigs, int32_t *track, unsigned long long *n_aln)
+{
+	const int lane = lane_id();
+	const uint32_t rd = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	if (rd >= B.n_reads) return;                              // (whole waves; the kernel has no workgroup barrier)
+	const int n = B.n_reg[rd];
+	if (n <= 0) return;
+	const int64_t slot0 = reg_slot(B, rd);
+	const int pick = sel == MNC_COV_ASSIGNED ? cov_pick(B, rd, slot0, n) : -1;
+	if (sel == MNC_COV_ASSIGNED && pick < 0) return;
+	for (int i = pick < 0 ? 0 : pick; i < (pick < 0 ? n : pick + 1); ++i) {
+		const mnc_reg_t r = B.regs[slot0 + i];
+		if (!cov_selected(r, sel, B.min_mapq) || r.rid < 0 || r.rid >= n_contigs) continue;
+		const int64_t len = off[r.rid + 1] - off[r.rid];
+		int32_t *w = track + off[r.rid];
+		if (lane == 0) (void)__hip_atomic_fetch_add(n_aln + r.rid, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const int n_c = r.n_cigar;
+		if (n_c <= 0) continue;
+		const uint32_t *src = B.cig_reg + B.regdp[slot0 + i].cig_off;
+		int64_t toff = r.rs;                                   // reference position before the chunk at hand
+		bool open = false;                                     // a run is open: the last M / D operation so far was an M
+		for (int k0 = 0; k0 < n_c; k0 += 64) {
+			const int k = k0 + lane;
+			const uint32_t wd = k < n_c ? src[k] : 0u;
+			const int op = (int)(wd & 0xfu);
+			const int l = k < n_c && op <= 2 ? (int)(wd >> 4) : 0;
+			const int dt = op != 1 ? l : 0;
+			const int it = cov_incl_add(dt);
+			const int64_t t0 = toff + it - dt;
+			const bool is_M = l > 0 && op == 0, is_D = l > 0 && op == 2;
+			const unsigned long long m_M = __ballot(is_M), m_D = __ballot(is_D);
+			const unsigned long long below = (m_M | m_D) & ((1ull << lane) - 1ull);
+			const bool prev_M = below ? (m_M >> (63 - __clzll((long long)below)) & 1ull) != 0 : open;
+			if (is_M && !prev_M) cov_put(w, len, t0, 1);
+			if (is_D && prev_M) cov_put(w, len, t0, -1);
+			const unsigned long long any = m_M | m_D;
+			if (any) open = (m_M >> (63 - __clzll((long long)any)) & 1ull) != 0;
+			toff += __shfl(it, 63);
+		}
+		if (open && lane == 0) cov_put(w, len, toff, -1);
+	}
+}
+
+__global__ __launch_bounds__(256) void mnc_cov_add_span(Batch B, int sel, const int64_t *off, int n_contigs, int32_t *track, unsigned long long *n_aln)
+{
+	const uint32_t rd = blockIdx.x * blockDim.x + threadIdx.x;
+	if (rd >= B.n_reads) return;
+	const int n = B.n_reg[rd];
+	if (n <= 0) return;
+	const int64_t slot0 = reg_slot(B, rd);
+	const int pick = sel == MNC_COV_ASSIGNED ? cov_pick(B, rd, slot0, n) : -1;
+	if (sel == MNC_COV_ASSIGNED && pick < 0) return;
+	for (int i = pick < 0 ? 0 : pick; i < (pick < 0 ? n : pick + 1); ++i) {
+		const mnc_reg_t &r = B.regs[slot0 + i];
+		if (!cov_selected(r, sel, B.min_mapq) || r.rid < 0 || r.rid >= n_contigs) continue;
+		const int64_t len = off[r.rid + 1] - off[r.rid];
+		int32_t *w = track + off[r.rid];
+		(void)__hip_atomic_fetch_add(n_aln + r.rid, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (r.re > r.rs) cov_put(w, len, r.rs, 1), cov_put(w, len, r.re, -1);
+	}
+}
+
+// G(off[c] - 1) of every contig: the exclusive tile sum of the tile that holds the contig's first word plus the words
+// of that tile in front of it (one wave per contig)
+__global__ __launch_bounds__(256) void mnc_cov_contig_base(const int32_t *track, const int64_t *off, int n_contigs, const int64_t *tile_pre, long long *cbase)
+{
+	const int c = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+	if (c >= n_contigs) return;
+	const int64_t s = off[c];
+	long long x = 0;
+	if (off[c + 1] > s) {                                      // (an empty contig has no word, and no tile, of its own)
+		const int64_t t = s / SC_TILE;
+		for (int64_t i = t * SC_TILE + lane_id(); i < s; i += 64) x += track[i];
+		for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
+		x += tile_pre[t];
+	}
+	if (lane_id() == 0) cbase[c] = x;
+}
+
+struct CovAcc {
+	int cov = 0, mx = 0, cnt = 0;
+	long long sum = 0;
+	__device__ __forceinline__ void add(int d) { cov += d > 0, sum += d, mx = d > mx ? d : mx, ++cnt; }
+};
+
+// MODE 0: the whole track, per-contig reductions.  MODE 1: the words of ONE contig (track points at its first), per-bin
+// reductions.  MODE 2: the first n words of one contig, depth of the words from `start` on written out.
+template <int MODE>
+__global__ __launch_bounds__(SC_THREADS) void mnc_cov_scan(const int32_t *track, int64_t n, const int64_t *tile_pre, const int64_t *off, int n_contigs,
+                                                           const long long *cbase, unsigned long long *o_cov, unsigned long long *o_sum, int32_t *o_max,
+                                                           int bin_bases, int32_t *b_cov, int64_t start, int32_t *depth)
+{
+	__shared__ long long s[SC_THREADS / 64];
+	__shared__ int s_c0;
+	__shared__ long long s_sum[SC_THREADS / 64];
+	__shared__ int s_cov[SC_THREADS / 64], s_max[SC_THREADS / 64];
+	const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
+	const int64_t tile0 = (int64_t)blockIdx.x * SC_TILE, base = tile0 + (int64_t)threadIdx.x * SC_ITEMS;
+	const int64_t tile_end = tile0 + SC_TILE < n ? tile0 + SC_TILE : n;
+	int v[SC_ITEMS];
+	long long x = 0;
+	for (int k = 0; k < SC_ITEMS; ++k) { v[k] = base + k < n ? track[base + k] : 0; x += v[k]; }
+	long long inc = x;
+	for (int d = 1; d < 64; d <<= 1) {
+		const long long o = __shfl_up(inc, d);
+		if (lane >= d) inc += o;
+	}
+	if (lane == 63) s[wave] = inc;
+	if (MODE == 0 && threadIdx.x == 0) {                       // the contig of the tile's first word: the last c with off[c] <= tile0
+		int lo = 0, hi = n_contigs;
+		while (hi - lo > 1) {
+			const int mid = lo + (hi - lo) / 2;
+			if (off[mid] <= tile0) lo = mid; else hi = mid;
+		}
+		s_c0 = lo;
+	}
+	__syncthreads();
+	long long pre = tile_pre[blockIdx.x] + inc - x;
+	for (int w = 0; w < wave; ++w) pre += s[w];
+	if (MODE == 0) {
+		const int c0 = s_c0;
+		if (tile_end <= off[c0 + 1]) {                            // (the same for the whole workgroup) the tile lies in one contig
+			const long long cb = cbase[c0];
+			CovAcc a;
+			for (int k = 0; k < SC_ITEMS; ++k) { pre += v[k]; if (base + k < n) a.add((int)(pre - cb)); }
+			for (int d = 32; d > 0; d >>= 1) {
+				a.cov += __shfl_xor(a.cov, d), a.sum += __shfl_xor(a.sum, d);
+				const int m = __shfl_xor(a.mx, d);
+				a.mx = m > a.mx ? m : a.mx;
+			}
+			if (lane == 0) s_cov[wave] = a.cov, s_sum[wave] = a.sum, s_max[wave] = a.mx;
+			__syncthreads();
+			if (threadIdx.x == 0) {
+				int cov = 0, mx = 0;
+				long long sum = 0;
+				for (int w = 0; w < SC_THREADS / 64; ++w) cov += s_cov[w], sum += s_sum[w], mx = s_max[w] > mx ? s_max[w] : mx;
+				if (cov) (void)atomicAdd(o_cov + c0, (unsigned long long)cov);
+				if (sum) (void)atomicAdd(o_sum + c0, (unsigned long long)sum);
+				if (mx > 0) (void)atomicMax(o_max + c0, mx);
+			}
+		} else if (base < n) {                                    // a contig border inside the tile: every lane for itself
+			int lo = 0, hi = n_contigs;
+			while (hi - lo > 1) {
+				const int mid = lo + (hi - lo) / 2;
+				if (off[mid] <= base) lo = mid; else hi = mid;
+			}
+			int c = lo;
+			CovAcc a;
+			auto flush = [&]() {
+				if (a.cov) (void)atomicAdd(o_cov + c, (unsigned long long)a.cov);
+				if (a.sum) (void)atomicAdd(o_sum + c, (unsigned long long)a.sum);
+				if (a.mx > 0) (void)atomicMax(o_max + c, a.mx);
+				a = CovAcc();
+			};
+			long long cb = cbase[c];
+			for (int k = 0; k < SC_ITEMS && base + k < n; ++k) {
+				while (c + 1 < n_contigs && base + k >= off[c + 1]) { flush(); ++c; cb = cbase[c]; }
+				pre += v[k];
+				a.add((int)(pre - cb));
+			}
+			flush();
+		}
+	} else if (MODE == 1) {
+		// a wave whose 256 words lie in one bin -- most, at the usual widths -- reduces first
+		const int64_t w_first = tile0 + (int64_t)wave * 64 * SC_ITEMS, w_last = (w_first + 64 * SC_ITEMS < n ? w_first + 64 * SC_ITEMS : n) - 1;
+		if (w_first < n && w_first / bin_bases == w_last / bin_bases) {
+			CovAcc a;
+			for (int k = 0; k < SC_ITEMS; ++k) { pre += v[k]; if (base + k < n) a.add((int)pre); }
+			for (int d = 32; d > 0; d >>= 1) a.cov += __shfl_xor(a.cov, d), a.sum += __shfl_xor(a.sum, d);
+			if (lane == 0) {
+				const int64_t b = w_first / bin_bases;
+				if (a.cov) (void)atomicAdd(b_cov + b, a.cov);
+				if (a.sum) (void)atomicAdd(o_sum + b, (unsigned long long)a.sum);
+			}
+		} else if (base < n) {
+			int64_t b = base / bin_bases;
+			CovAcc a;
+			for (int k = 0; k < SC_ITEMS && base + k < n; ++k) {
+				const int64_t bk = (base + k) / bin_bases;
+				if (bk != b) {
+					if (a.cov) (void)atomicAdd(b_cov + b, a.cov);
+					if (a.sum) (void)atomicAdd(o_sum + b, (unsigned long long)a.sum);
+					a = CovAcc(), b = bk;
+				}
+				pre += v[k];
+				a.add((int)pre);
+			}
+			if (a.cov) (void)atomicAdd(b_cov + b, a.cov);
+			if (a.sum) (void)atomicAdd(o_sum + b, (unsigned long long)a.sum);
+		}
+	} else {
+		for (int k = 0; k < SC_ITEMS; ++k) {
+			pre += v[k];
+			if (base + k < n && base + k >= start) depth[base + k - start] = (int32_t)pre;
+		}
+	}
+}
+
+// tile sums of track[0 .. n) (exclusive, in place), then the pass of MODE over the tiles
+template <int MODE>
+static void cov_launch_scan(mnc_coverage *cv, const int32_t *track, int64_t n, int32_t *b_cov, unsigned long long *b_sum, int64_t start, int32_t *depth)
+{
+	const int64_t nb = (n + SC_TILE - 1) / SC_TILE;
+	hipStream_t st = cv->st;
+	hipLaunchKernelGGL(mnc_scan_reduce<ScanInPlain<int32_t>>, dim3((unsigned)nb), dim3(SC_THREADS), 0, st, ScanInPlain<int32_t>{track}, n, cv->tile_sums);
+	hipLaunchKernelGGL(mnc_scan_sums, dim3(1), dim3(64), 0, st, cv->tile_sums, nb);
+	if (MODE == 0) hipLaunchKernelGGL(mnc_cov_contig_base, dim3((unsigned)((cv->n_contigs + 3) / 4)), dim3(256), 0, st, track, cv->d_off, cv->n_contigs, cv->tile_sums, cv->cbase);
+	hipLaunchKernelGGL(mnc_cov_scan<MODE>, dim3((unsigned)nb), dim3(SC_THREADS), 0, st, track, n, cv->tile_sums, cv->d_off, cv->n_contigs, cv->cbase,
+	                   MODE == 0 ? cv->c_cov : nullptr, MODE == 0 ? cv->c_sum : b_sum, MODE == 0 ? cv->c_max : nullptr, cv->bin_bases, b_cov, start, depth);
+}
+
+// ---------------------------------------------------------------- the engine's side (mnc_engine_add_coverage, engine.hip)
+const mnc_index *coverage_index(const mnc_coverage *cv) { return cv->idx; }
+int coverage_device_of(const mnc_coverage *cv) { return cv->device; }
+
+// the batch B, as it stands in HBM, on the engine's stream `st`; nothing waits on the host
+int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream_t st)
+{
+	if (B.n_reads == 0 || cv->n_words == 0) return MNC_OK;
+	HIP_TRY(hipStreamWaitEvent(st, cv->ev_own, 0));            // behind the last reset
+	if (span) hipLaunchKernelGGL(mnc_cov_add_span, dim3((B.n_reads + 255) / 256), dim3(256), 0, st, B, sel, cv->d_off, cv->n_contigs, cv->track, cv->n_aln);
+	else hipLaunchKernelGGL(mnc_cov_add_runs, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, cv->d_off, cv->n_contigs, cv->track, cv->n_aln);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(cv->ev_add, st));
+	HIP_TRY(hipStreamWaitEvent(cv->st, cv->ev_add, 0));        // reset and the summaries come after it
+	return MNC_OK;
+}
+
+} // namespace mnc
+
+// ---------------------------------------------------------------- C-ABI
+extern "C" void mnc_coverage_free(mnc_coverage *cv)
+{
+	if (!cv) return;
+	(void)hipSetDevice(cv->device);
+	if (cv->st) (void)hipStreamSynchronize(cv->st);
+	for (void *p : { (void*)cv->track, (void*)cv->n_aln, (void*)cv->d_off, (void*)cv->tile_sums, (void*)cv->cbase, (void*)cv->c_cov, (void*)cv->c_sum, (void*)cv->c_max })
+		if (p) (void)hipFree(p);
+	if (cv->ev_add) (void)hipEventDestroy(cv->ev_add);
+	if (cv->ev_own) (void)hipEventDestroy(cv->ev_own);
+	if (cv->st) (void)hipStreamDestroy(cv->st);
+	delete cv;
+}
+
+extern "C" int mnc_coverage_create(mnc_index *idx, int device, int bin_bases, mnc_coverage **out)
+{
+	if (!idx || !out) return MNC_ERR_ARG;
+	*out = nullptr;
+	if (bin_bases < 1) { set_error("bin_bases must be 1 or more"); return MNC_ERR_ARG; }
+	if (int rc = check_device(device)) return rc;
+	mnc_coverage *cv = new (std::nothrow) mnc_coverage;
+	if (!cv) return MNC_ERR_NOMEM;
+	cv->idx = idx, cv->device = device, cv->bin_bases = bin_bases, cv->n_contigs = (int)idx->contig_len.size();
+	try {
+		cv->off.assign((size_t)cv->n_contigs + 1, 0);
+	} catch (const std::bad_alloc &) { delete cv; return MNC_ERR_NOMEM; }
+	for (int c = 0; c < cv->n_contigs; ++c) cv->off[c + 1] = cv->off[c] + idx->contig_len[c];
+	cv->n_words = cv->off[cv->n_contigs];
+	const size_t nc = (size_t)cv->n_contigs, nw = (size_t)cv->n_words;
+	hipError_t he = hipSetDevice(device);
+	auto alloc = [&](void **p, size_t bytes) {
+		if (he != hipSuccess) return;
+		bytes = bytes ? bytes : 8;
+		he = hipMalloc(p, bytes);
+		if (he == hipSuccess) cv->bytes += (int64_t)bytes; else *p = nullptr;
+	};
+	alloc((void**)&cv->track, nw * 4);
+	alloc((void**)&cv->n_aln, nc * 8);
+	alloc((void**)&cv->d_off, (nc + 1) * 8);
+	alloc((void**)&cv->tile_sums, (nw / SC_TILE + 2) * 8);
+	alloc((void**)&cv->cbase, nc * 8);
+	alloc((void**)&cv->c_cov, nc * 8);
+	alloc((void**)&cv->c_sum, nc * 8);
+	alloc((void**)&cv->c_max, nc * 4);
+	const bool nomem = he == hipErrorOutOfMemory;
+	if (he == hipSuccess) he = hipStreamCreateWithFlags(&cv->st, hipStreamNonBlocking);
+	if (he == hipSuccess) he = hipEventCreateWithFlags(&cv->ev_add, hipEventDisableTiming);
+	if (he == hipSuccess) he = hipEventCreateWithFlags(&cv->ev_own, hipEventDisableTiming);
+	if (he == hipSuccess) he = hipMemcpy(cv->d_off, cv->off.data(), (nc + 1) * 8, hipMemcpyHostToDevice);
+	if (he != hipSuccess) {
+		set_error("coverage accumulator of %lld bases: %s", (long long)cv->n_words, hipGetErrorString(he));
+		(void)hipGetLastError();
+		mnc_coverage_free(cv);
+		return nomem ? MNC_ERR_NOMEM : MNC_ERR_HIP;
+	}
+	if (int rc = mnc_coverage_reset(cv)) { mnc_coverage_free(cv); return rc; }
+	*out = cv;
+	return MNC_OK;
+}
+
+extern "C" int mnc_coverage_reset(mnc_coverage *cv)
+{
+	if (!cv) return MNC_ERR_ARG;
+	HIP_TRY(hipSetDevice(cv->device));
+	if (cv->n_words) HIP_TRY(hipMemsetAsync(cv->track, 0, (size_t)cv->n_words * 4, cv->st));
+	if (cv->n_contigs) HIP_TRY(hipMemsetAsync(cv->n_aln, 0, (size_t)cv->n_contigs * 8, cv->st));
+	HIP_TRY(hipEventRecord(cv->ev_own, cv->st));
+	return MNC_OK;
+}
+
+extern "C" int mnc_coverage_device_bytes(const mnc_coverage *cv, int64_t *bytes)
+{
+	if (!cv || !bytes) return MNC_ERR_ARG;
+	*bytes = cv->bytes;
+	return MNC_OK;
+}
+
+extern "C" int mnc_coverage_summary(mnc_coverage *cv, int64_t *covered, int64_t *depth_sum, int32_t *max_depth, int64_t *n_aln)
+{
+	if (!cv) return MNC_ERR_ARG;
+	HIP_TRY(hipSetDevice(cv->device));
+	const size_t nc = (size_t)cv->n_contigs;
+	hipStream_t st = cv->st;
+	if (nc && (covered || depth_sum || max_depth)) {
+		HIP_TRY(hipMemsetAsync(cv->c_cov, 0, nc * 8, st));
+		HIP_TRY(hipMemsetAsync(cv->c_sum, 0, nc * 8, st));
+		HIP_TRY(hipMemsetAsync(cv->c_max, 0, nc * 4, st));
+		if (cv->n_words) cov_launch_scan<0>(cv, cv->track, cv->n_words, nullptr, nullptr, 0, nullptr);
+		HIP_TRY(hipGetLastError());
+		if (covered) HIP_TRY(hipMemcpyAsync(covered, cv->c_cov, nc * 8, hipMemcpyDeviceToHost, st));
+		if (depth_sum) HIP_TRY(hipMemcpyAsync(depth_sum, cv->c_sum, nc * 8, hipMemcpyDeviceToHost, st));
+		if (max_depth) HIP_TRY(hipMemcpyAsync(max_depth, cv->c_max, nc * 4, hipMemcpyDeviceToHost, st));
+	}
+	if (nc && n_aln) HIP_TRY(hipMemcpyAsync(n_aln, cv->n_aln, nc * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return MNC_OK;
+}
+
+extern "C" int mnc_coverage_fetch_bins(mnc_coverage *cv, int rid, int32_t *bin_covered, int64_t *bin_depth_sum, int64_t cap, int64_t *n_bins)
+{
+	if (!cv || !n_bins) return MNC_ERR_ARG;
+	if (rid < 0 || rid >= cv->n_contigs) { set_error("contig %d out of range", rid); return MNC_ERR_ARG; }
+	const int64_t len = cv->off[rid + 1] - cv->off[rid], nb = (len + cv->bin_bases - 1) / cv->bin_bases;
+	*n_bins = nb;
+	if (cap < nb) { set_error("contig %d has %lld bins of %d bases", rid, (long long)nb, cv->bin_bases); return MNC_ERR_RANGE; }
+	if (nb == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(cv->device));
+	hipStream_t st = cv->st;
+	char *tmp = nullptr;                                        // [nb] depth sums, then [nb] covered bases
+	HIP_TRY(hipMalloc((void**)&tmp, (size_t)nb * 12));
+	int rc = MNC_OK;
+	hipError_t he = hipMemsetAsync(tmp, 0, (size_t)nb * 12, st);
+	if (he == hipSuccess) {
+		cov_launch_scan<1>(cv, cv->track + cv->off[rid], len, (int32_t*)(tmp + (size_t)nb * 8), (unsigned long long*)tmp, 0, nullptr);
+		he = hipGetLastError();
+	}
+	if (he == hipSuccess && bin_depth_sum) he = hipMemcpyAsync(bin_depth_sum, tmp, (size_t)nb * 8, hipMemcpyDeviceToHost, st);
+	if (he == hipSuccess && bin_covered) he = hipMemcpyAsync(bin_covered, tmp + (size_t)nb * 8, (size_t)nb * 4, hipMemcpyDeviceToHost, st);
+	const hipError_t hs = hipStreamSynchronize(st);
+	if (he == hipSuccess) he = hs;
+	if (he != hipSuccess) { set_error("bins of contig %d: %s", rid, hipGetErrorString(he)); rc = MNC_ERR_HIP; }
+	(void)hipFree(tmp);
+	return rc;
+}
+
+extern "C" int mnc_coverage_fetch_depth(mnc_coverage *cv, int rid, int64_t start, int64_t end, int32_t *depth)
+{
+	if (!cv) return MNC_ERR_ARG;
+	if (rid < 0 || rid >= cv->n_contigs) { set_error("contig %d out of range", rid); return MNC_ERR_ARG; }
+	const int64_t len = cv->off[rid + 1] - cv->off[rid];
+	if (start < 0 || end < start || end > len) {
+		set_error("interval [%lld, %lld) outside contig %d of %lld bases", (long long)start, (long long)end, rid, (long long)len);
+		return MNC_ERR_ARG;
+	}
+	if (end == start) return MNC_OK;
+	if (!depth) return MNC_ERR_ARG;
+	HIP_TRY(hipSetDevice(cv->device));
+	hipStream_t st = cv->st;
+	int32_t *tmp = nullptr;
+	HIP_TRY(hipMalloc((void**)&tmp, (size_t)(end - start) * 4));
+	int rc = MNC_OK;
+	cov_launch_scan<2>(cv, cv->track + cv->off[rid], end, nullptr, nullptr, start, tmp);   // the contig's words up to `end`: the sum starts at the contig
+	hipError_t he = hipGetLastError();
+	if (he == hipSuccess) he = hipMemcpyAsync(depth, tmp, (size_t)(end - start) * 4, hipMemcpyDeviceToHost, st);
+	const hipError_t hs = hipStreamSynchronize(st);
+	if (he == hipSuccess) he = hs;
+	if (he != hipSuccess) { set_error("depth of contig %d: %s", rid, hipGetErrorString(he)); rc = MNC_ERR_HIP; }
+	(void)hipFree(tmp);
+	return rc;
+}
+
+extern "C" int mnc_coverage_device(mnc_coverage *cv, const int32_t **d_track, int64_t *n_words)
+{
+	if (!cv) return MNC_ERR_ARG;
+	if (d_track) *d_track = cv->n_words ? cv->track : nullptr;
+	if (n_words) *n_words = cv->n_words;
+	return MNC_OK;
+}
