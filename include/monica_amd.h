@@ -182,6 +182,13 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   MNC_CONTRACT_CHAIN
  *   a reference base overlapped by 2^31 or more  outside the contract: the depth track holds int32 (mnc_coverage_reset
  *   added records                                starts over)
+ *   pileup after a call that ran both the usual  mnc_engine_add_pileup: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
+ *   and the wide pass                            coverage); a call whose reads are all long adds like any other
+ *   pileup under MNC_CONTRACT_CHAIN              mnc_engine_add_pileup: MNC_ERR_ARG (no CIGAR to take the columns from)
+ *   the bases of an insertion                    inserted bases are not stored: mnc_pileup counts an insertion once, at the
+ *                                                reference base on its left, whatever it inserts
+ *   a reference base with 2^31 or more           outside the contract: every plane of mnc_pileup holds int32 per base
+ *   observations in one pileup plane             (mnc_pileup_reset starts over)
  */
 
 /* ---------------------------------------------------------------- classify
@@ -463,6 +470,98 @@ int  mnc_coverage_fetch_depth(mnc_coverage *cov, int rid, int64_t start, int64_t
  * first word and is dropped, so a contig's words need not sum to zero.  Ordered behind the adds only after
  * mnc_coverage_summary or a sync of the engines that added. */
 int  mnc_coverage_device(mnc_coverage *cov, const int32_t **d_track, int64_t *n_words);
+
+/* ---------------------------------------------------------------- pileup
+ * What the reads say at each reference base: allele counts, variants and a consensus, the question the reference's focus
+ * pass (`-F`, "focus analysis on their subspecies") is asked -- two strains 0.5 % apart differ at a few thousand positions.
+ * An mnc_pileup sits beside mnc_coverage and has its lifetime rules: it belongs to one index on one device, lives across
+ * classify calls, is added to from the last batch as it stands in HBM (regions, region CIGARs, the reads' bases, the
+ * contigs' 4-bit store; csrc/k_pileup.hip) asynchronously on the engine's stream with no host wait, and runs only when
+ * asked for: a batch that does not ask costs not one more kernel, allocation or byte.  Unlike mnc_coverage, engines of the
+ * same index and device may add to one mnc_pileup from their own threads at the same time; reset and the read-outs are for
+ * one thread at a time.
+ *
+ * What a call adds -- `what` = exactly ONE of MNC_COV_GATED / PRIMARY / ALL / ASSIGNED, with the meaning they have for
+ * coverage (MNC_COV_SPAN has none here: MNC_ERR_ARG).  A selected record's CIGAR is walked from rs on the contig; its query
+ * columns are taken on the hit's strand, as cs and MD take them: column p of the query side is read base qs + p for
+ * rev = 0 and the COMPLEMENT of read base qe - 1 - p for rev = 1.  A read base counts as A, C, G or T in either case
+ * (U / u as T), as N otherwise; a reference base r is A, C, G, T, or N for anything else in the 4-bit store.  Per column:
+ *   M column at reference base p, query base b   depth[p] += 1 (the M columns of coverage without MNC_COV_SPAN) and one
+ *                                                observation of b at p: count[b][p] += 1, b one of A C G T N
+ *   D operation                                  del[p] += 1 for every base p under it (depth is not touched)
+ *   I operation                                  ins[q] += 1 ONCE per operation, whatever its length: q is the reference
+ *                                                position of the last reference-consuming column before it in that record.
+ *                                                An I with no such column is not counted (mm_fix_cigar leaves none).
+ *                                                THE INSERTED BASES ARE NOT STORED: an insertion is known by place and count
+ * The result is eight planes per reference base, in this order: depth, A, C, G, T, N, DEL, INS (MNC_PILE_*), all exact
+ * integers.  Addition commutes: the result does not depend on order or on how a sample was cut into batches.
+ * Derived: span[p] = depth[p] + del[p], the records that say something about base p.
+ *
+ * Storage (what mnc_pileup_device hands out; 32 bytes of HBM per reference base): most columns match the reference, so a
+ * column does not cost an atomic.  Word w of every plane below is base p of contig c with w = (sum of the lengths of
+ * contigs 0 .. c - 1) + p, the layout of mnc_coverage_device:
+ *   d_depth  int32[n_words]      depth DIFFERENCES, exactly mnc_coverage's track: +1 where a run of M columns starts, -1
+ *                                one past its end, the -1 that would fall on the next contig's first word dropped;
+ *                                depth(c, p) = the sum of contig c's words 0 .. p
+ *   d_alt    int32[7][n_words]   channel-major, channels A C G T N DEL INS: an M column adds to its query base's channel
+ *                                only where it is NOT a reference match -- a mismatch, a query N, or any column over a
+ *                                reference N (which adds to its own base's channel); DEL and INS as above
+ *   count[b][p] = alt[b][p] + (r == b ? depth[p] - (alt[A] + alt[C] + alt[G] + alt[T] + alt[N])[p] : 0)   for b in A C G T
+ *   count[N][p] = alt[N][p]
+ * Every word is additive, the depth differences included: ranks sum the 8 * n_words words with one collective of their own. */
+typedef struct mnc_pileup mnc_pileup;
+#define MNC_PILE_DEPTH 0
+#define MNC_PILE_A     1
+#define MNC_PILE_C     2
+#define MNC_PILE_G     3
+#define MNC_PILE_T     4
+#define MNC_PILE_N     5
+#define MNC_PILE_DEL   6
+#define MNC_PILE_INS   7
+#define MNC_PILE_PLANES 8
+/* one called variant (mnc_pileup_call_variants): 20 bytes */
+typedef struct {
+	int32_t rid, pos;            /* contig, 0-based reference position (an insertion: the base on its left) */
+	int32_t span;                /* depth + del at pos */
+	int32_t count;               /* observations of `alt` at pos */
+	uint8_t ref;                 /* 'A' 'C' 'G' 'T' */
+	uint8_t alt;                 /* 'A' 'C' 'G' 'T', '-' (deleted), '+' (an insertion follows; its bases are not stored) */
+	uint8_t pad[2];              /* 0 */
+} mnc_variant_t;
+/* MNC_ERR_NODEVICE without a gfx950 device, MNC_ERR_ARG for an index without contig bases, MNC_ERR_NOMEM when the 32 bytes
+ * per reference base do not fit the HBM that is free (3.0 GB for an index of 94 Mbp). */
+int  mnc_pileup_create(mnc_index *idx, int device, mnc_pileup **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_pileup_free(mnc_pileup *pu);
+/* clears every plane; asynchronous */
+int  mnc_pileup_reset(mnc_pileup *pu);
+/* HBM the accumulator holds: 32 bytes per reference base, a few words per contig and 24 bytes per 1 024 bases of scratch */
+int  mnc_pileup_device_bytes(const mnc_pileup *pu, int64_t *bytes);
+/* The raw additive planes (device pointers), laid out as above; either pointer may be NULL.  Ordered behind the adds only
+ * after a read-out call below or a sync of the engines that added. */
+int  mnc_pileup_device(mnc_pileup *pu, const int32_t **d_depth, const int32_t **d_alt, int64_t *n_words);
+/* Adds the last classified batch of `eng` as it stands in HBM.  Needs no mnc_engine_export_alignments and disturbs none.
+ * Asynchronous on the engine's stream, no host wait.  MNC_ERR_ARG: `pu` is for another index or device than the engine's
+ * current ones; no selector, more than one, or MNC_COV_SPAN; no batch has been classified yet; MNC_CONTRACT_CHAIN (no
+ * CIGAR).  MNC_ERR_UNSUPPORTED: the last call ran both the usual and the wide pass (the engine holds the wide pass alone);
+ * a call whose reads are all long adds like any other.  The accumulator is untouched on any error. */
+int  mnc_engine_add_pileup(mnc_engine *eng, mnc_pileup *pu, int what);
+/* The eight planes of bases [start, end) of contig rid, plane-major: out[k * (end - start) + (p - start)], k = MNC_PILE_*.
+ * The interval is checked as by mnc_index_getseq (MNC_ERR_ARG).  Waits for the work queued so far and leaves the
+ * accumulator as it is, like every read-out below. */
+int  mnc_pileup_fetch_counts(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t *out /* [8][end - start] */);
+/* The variants of contig rid, or of every contig for rid = -1, compacted in (rid, pos, allele) order, the alleles of a
+ * position in the order A, C, G, T, DEL, INS.  An allele with count c at a base with reference base r is called iff r is
+ * not N, the allele is not r, span >= min_depth, c >= min_count and c * 1000 >= min_permille * span (compared in int64:
+ * no floating point anywhere).  *n = the number of variants; MNC_ERR_RANGE, with *n set and nothing written, when cap is
+ * short; MNC_ERR_ARG for a bad rid.  Two passes on the device -- count, scan, write -- so only the variants travel. */
+int  mnc_pileup_call_variants(mnc_pileup *pu, int rid, int32_t min_depth, int32_t min_count, int32_t min_permille,
+                              mnc_variant_t *out, int64_t cap, int64_t *n);
+/* One character per base of [start, end) of contig rid (not NUL-terminated; the interval checked as above): 'N' where
+ * span < min_depth; otherwise the largest of the counts of A, C, G, T and DEL -- on a tie the reference base if it is
+ * among the tied, else the first of them in that order -- written 'A' 'C' 'G' 'T' or '-'.  Insertions do not appear:
+ * their bases are not stored. */
+int  mnc_pileup_consensus(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t min_depth, char *out /* end - start */);
 
 /* ---------------------------------------------------------------- FASTQ batches and read routing
  * Replaces the per-record Biopython objects of the reference's loop:

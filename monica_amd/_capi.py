@@ -42,6 +42,10 @@ PAF_PRIMARY_ONLY = 1
 COV_GATED, COV_PRIMARY, COV_ALL, COV_ASSIGNED, COV_SPAN = 1, 2, 4, 8, 16
 # one row per contig of Coverage.summary()
 COV_SUMMARY_DTYPE = np.dtype([("covered", "<i8"), ("depth_sum", "<i8"), ("max_depth", "<i4"), ("n_aln", "<i8")])
+# the planes of Pileup.counts(), in order (MNC_PILE_*), and one row of Pileup.variants() (mnc_variant_t, 20 bytes)
+PILE_PLANES = ("depth", "A", "C", "G", "T", "N", "DEL", "INS")
+VARIANT_DTYPE = np.dtype([("rid", "<i4"), ("pos", "<i4"), ("span", "<i4"), ("count", "<i4"), ("ref", "S1"), ("alt", "S1"), ("pad", "<u2")])
+assert VARIANT_DTYPE.itemsize == 20
 MZ_DTYPE = np.dtype([("hash", "<u4"), ("pos_strand", "<u4")])
 ANCHOR_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8")])
 
@@ -80,6 +84,8 @@ EXPORTS = [
     "mnc_index_getseq", "mnc_fastq_write_paf",
     "mnc_coverage_create", "mnc_coverage_free", "mnc_coverage_reset", "mnc_coverage_device_bytes", "mnc_engine_add_coverage",
     "mnc_coverage_summary", "mnc_coverage_fetch_bins", "mnc_coverage_fetch_depth", "mnc_coverage_device",
+    "mnc_pileup_create", "mnc_pileup_free", "mnc_pileup_reset", "mnc_pileup_device_bytes", "mnc_pileup_device", "mnc_engine_add_pileup",
+    "mnc_pileup_fetch_counts", "mnc_pileup_call_variants", "mnc_pileup_consensus",
 ]
 
 
@@ -220,6 +226,15 @@ def lib():
     sig("mnc_coverage_fetch_bins", i32, [vp, i32, vp, vp, i64, C.POINTER(i64)])
     sig("mnc_coverage_fetch_depth", i32, [vp, i32, i64, i64, vp])
     sig("mnc_coverage_device", i32, [vp, pp, C.POINTER(i64)])
+    sig("mnc_pileup_create", i32, [vp, i32, pp])
+    sig("mnc_pileup_free", None, [vp])
+    sig("mnc_pileup_reset", i32, [vp])
+    sig("mnc_pileup_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_pileup_device", i32, [vp, pp, pp, C.POINTER(i64)])
+    sig("mnc_engine_add_pileup", i32, [vp, vp, i32])
+    sig("mnc_pileup_fetch_counts", i32, [vp, i32, i64, i64, vp])
+    sig("mnc_pileup_call_variants", i32, [vp, i32, i32, i32, i32, vp, i64, C.POINTER(i64)])
+    sig("mnc_pileup_consensus", i32, [vp, i32, i64, i64, i32, vp])
     _LIB = L
     return L
 
@@ -552,6 +567,11 @@ class Engine:
         `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED, optionally | COV_SPAN.  Asynchronous."""
         check(lib().mnc_engine_add_coverage(self._h, cov._h if cov is not None else None, int(what)))
 
+    def add_pileup(self, pileup, what=COV_GATED):
+        """`mnc_engine_add_pileup`: add the last classified batch, as it stands in HBM, to the accumulator `pileup`.
+        `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
+        check(lib().mnc_engine_add_pileup(self._h, pileup._h if pileup is not None else None, int(what)))
+
     def set_profiling(self, on=True):
         check(lib().mnc_engine_set_profiling(self._h, 1 if on else 0))
 
@@ -675,6 +695,74 @@ class Coverage:
     def close(self):
         if getattr(self, "_h", None):
             lib().mnc_coverage_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------------- pileup
+class Pileup:
+    """Owner of an ``mnc_pileup``: what the reads say at every reference base of one index on one device -- depth, the
+    counts of A C G T N, deletions and insertions -- accumulated from batch to batch by `Engine.add_pileup`
+    (include/monica_amd.h, "pileup")."""
+
+    def __init__(self, index, device=0):
+        self.index = index
+        self._device = device                                   # (`device` is the method below)
+        h = C.c_void_p()
+        check(lib().mnc_pileup_create(index._h if index is not None else None, int(device), C.byref(h)))
+        self._h = h
+
+    def reset(self):
+        check(lib().mnc_pileup_reset(self._h))
+
+    def device_bytes(self):
+        n = C.c_int64(0)
+        check(lib().mnc_pileup_device_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    def _end(self, rid, end):
+        return (self.index.contig_lens[rid] if 0 <= rid < len(self.index.contig_lens) else 0) if end is None else int(end)
+
+    def counts(self, rid, start=0, end=None):
+        """The eight planes (PILE_PLANES) of bases [start, end) of contig `rid`: int32[8, end - start]."""
+        end = self._end(rid, end)
+        out = np.zeros((len(PILE_PLANES), max(end - int(start), 0)), dtype=np.int32)
+        check(lib().mnc_pileup_fetch_counts(self._h, int(rid), int(start), end, out.ctypes.data if out.size else None))
+        return out
+
+    def variants(self, rid=-1, min_depth=1, min_count=1, min_permille=0):
+        """The called variants (VARIANT_DTYPE) of contig `rid`, or of every contig for -1, in (rid, pos, allele) order."""
+        n = C.c_int64(0)
+        args = (int(rid), int(min_depth), int(min_count), int(min_permille))
+        rc = lib().mnc_pileup_call_variants(self._h, *args, None, 0, C.byref(n))
+        if rc not in (OK, ERR_RANGE):
+            check(rc)
+        out = np.zeros(n.value, dtype=VARIANT_DTYPE)
+        if len(out):
+            check(lib().mnc_pileup_call_variants(self._h, *args, out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
+    def consensus(self, rid, start=0, end=None, min_depth=1):
+        """One byte per base of [start, end) of contig `rid`: A C G T, '-' (deleted) or N (span < min_depth)."""
+        end = self._end(rid, end)
+        out = np.zeros(max(end - int(start), 0), dtype=np.uint8)
+        check(lib().mnc_pileup_consensus(self._h, int(rid), int(start), end, int(min_depth), out.ctypes.data if len(out) else None))
+        return out.tobytes()
+
+    def device(self):
+        """(device address of the depth differences, of the seven alt planes, words per plane): `mnc_pileup_device`."""
+        d, a, n = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        check(lib().mnc_pileup_device(self._h, C.byref(d), C.byref(a), C.byref(n)))
+        return int(d.value or 0), int(a.value or 0), int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mnc_pileup_free(self._h)
             self._h = None
 
     def __del__(self):

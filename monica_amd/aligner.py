@@ -66,6 +66,9 @@ BATCH_BASES = min(1 << 27, BATCH_READS * 6000)
 BATCH_RAMP = tuple(float(x) for x in os.environ.get("MONICA_AMD_BATCH_RAMP", "0.25").split(",") if x.strip())
 COVERAGE_BIN_BASES = 1024         # `coverage=True`: the bin width of the sample's accumulator
 COVERAGE_CSV_HEADER = ("genome", "contig", "length", "covered_bases", "breadth", "mean_depth", "alignments")
+# `pileup=True`: (min_depth, min_count, min_permille) of the sample's variant calls; a 3-tuple in its place sets its own
+PILEUP_THRESHOLDS = (5, 3, 500)
+VARIANTS_TSV_HEADER = ("genome", "contig", "pos", "ref", "alt", "count", "span", "permille")
 DEFAULT_MAX_WORKERS = int(os.environ.get("MONICA_AMD_MAX_WORKERS", "8"))   # `n_threads=None`: at most this many samples in flight
 TIMINGS = {}                      # per sample name: seconds spent per phase of aligner() (diagnostics)
 PIPE_TRACE = [] if os.environ.get("MONICA_AMD_PIPE_TRACE") else None   # (stage, reads, start, end) per batch and stage (diagnostics)
@@ -124,10 +127,10 @@ def index_loader(index_file):
 def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quality=60, overnight=False, n_threads=None,
                            focus_species=[], output_folder=None, mapped_files_folder=MAPPED_FILES_FOLDER,
                            unmapped_files_folder=UNMAPPED_FILES_FOLDER, ambiguous_files_folder=AMBIGUOUS_FILES_FOLDER,
-                           hits_files_folder=HITS_FILES_FOLDER, focus_file_folder=FOCUS_FILES_FOLDER, coverage=None):
+                           hits_files_folder=HITS_FILES_FOLDER, focus_file_folder=FOCUS_FILES_FOLDER, coverage=None, pileup=None):
     """Classify every non-empty `*fastq` file of `query_folder` against the index parts
     (aligner.py:65-111): every part but the last only collects hits; the last part decides.
-    `coverage` (not in the reference; off by default): see `aligner_coverage`."""
+    `coverage`, `pileup` (not in the reference; off by default): see `aligner_coverage`."""
     os.chdir(query_folder)
     samples = [f for f in os.listdir(".") if f.endswith("fastq") and os.stat(f).st_size]
     if not samples:
@@ -154,19 +157,20 @@ def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quali
     pool = ThreadPool(workers)
     rep = itertools.repeat
     mappy.reserve_index_cache(len(indexes_paths))
+    extra = [rep(coverage), rep(pileup)] if coverage or pileup else []     # the arguments `aligner` does not have
     try:
         for part in indexes_paths[:-1]:
             index = index_loader(part)
-            pool.starmap(aligner_coverage if coverage else aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
+            pool.starmap(aligner_coverage if extra else aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
                                       rep(mapping_quality), *([rep(False), rep([]), rep(None), rep(None), rep(None), rep(None),
-                                                               rep(False), rep(coverage)] if coverage else [])))
+                                                               rep(False)] + extra if extra else [])))
         index = index_loader(indexes_paths[-1])
         _trace("loaded", 0, time.perf_counter())
-        results = pool.starmap(aligner_coverage if coverage else aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
+        results = pool.starmap(aligner_coverage if extra else aligner, zip(samples, samples_name, rep(index), rep(mode), rep(folders["hits"]),
                                             rep(mapping_quality), rep(overnight), rep(focus_species),
                                             rep(folders["mapped"]), rep(folders["unmapped"]),
                                             rep(folders["ambiguous"]), rep(folders["focus"]), rep(True),
-                                            *([rep(coverage)] if coverage else [])))
+                                            *extra))
     finally:
         _trace("mapped", 0, time.perf_counter())
         pool.close()
@@ -189,10 +193,10 @@ def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_qua
 
 def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, mapping_quality=None, overnight=False,
                      focus_species=[], mapped_folder=None, unmapped_folder=None, ambiguous_folder=None, focus_folder=None,
-                     last_index=False, coverage=None):
-    """One sample file against one index part (aligner.py:179-279): `aligner` and the opt-in `coverage=` argument, which
-    the reference does not have (`aligner` itself keeps the reference's parameter list; `multi_threaded_aligner(...,
-    coverage=)` calls this one).
+                     last_index=False, coverage=None, pileup=None):
+    """One sample file against one index part (aligner.py:179-279): `aligner` and the opt-in `coverage=` and `pileup=`
+    arguments, which the reference does not have (`aligner` itself keeps the reference's parameter list;
+    `multi_threaded_aligner(..., coverage=, pileup=)` calls this one).
 
     `coverage` (None / False: off, and nothing changes -- same outputs, same files): True, or the
     bin width in bases, makes a device accumulator for this sample and index part (`mappy_compat.Aligner.coverage`),
@@ -202,6 +206,12 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     known only after the last part, so coverage is collected with `COV_GATED` per part -- every record that passes the
     gate, in every part's own rows.  A batch that mixes reads of 2^20 bases or more with shorter ones (long reads on)
     cannot be added (include/monica_amd.h, "limits") and is reported.  The return value is as ever.
+
+    `pileup` (None / False: off, and nothing changes -- same outputs, same files): True, or a tuple (min_depth,
+    min_count, min_permille) in place of `PILEUP_THRESHOLDS`, makes a per-base pileup for this sample and index part
+    (`mappy_compat.Aligner.pileup`), adds every batch to it and leaves `<sample_name>.variants.tsv`
+    (`VARIANTS_TSV_HEADER`, one row per called variant, positions 0-based) beside the coverage CSV.  It is collected with
+    `COV_GATED` per part, for the reason above: a variant file must not depend on which part came last.
 
     Per batch: the library parses the FASTQ records (`mnc_fastq_next`), the GPU classifies them
     (`mnc_classify_batch`), the per-id hit lists carried over from earlier index parts are
@@ -224,6 +234,7 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     if coverage:
         cov = index.coverage(COVERAGE_BIN_BASES if coverage is True else int(coverage))
         cov_what = _capi.COV_ASSIGNED if last_index and not os.path.exists(carried_file) else _capi.COV_GATED
+    pile = index.pileup() if pileup else None
 
     clock = TIMINGS.setdefault(sample_name, dict.fromkeys(("parse", "classify", "carry", "route", "count", "engine", "open", "close", "remove"), 0.0))
     clock["engine"] += t_engine
@@ -334,6 +345,13 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
                 if err.code != _capi.ERR_UNSUPPORTED:
                     raise
                 print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no coverage")
+        if pile is not None:
+            try:
+                engine.add_pileup(pile, _capi.COV_GATED)      # asynchronous likewise
+            except _capi.MncError as err:
+                if err.code != _capi.ERR_UNSUPPORTED:
+                    raise
+                print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no pileup")
         clock["classify"] += time.perf_counter() - t1
         _trace("classify", batch.n, t1)
         n_skipped = int((out[0] == _capi.SKIPPED).sum())
@@ -480,6 +498,14 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
                 write_coverage_csv(cov, os.path.join(mapped_folder if last_index else hits_folder, sample_name + ".coverage.csv"))
         finally:
             cov.close()
+    if pile is not None:
+        try:
+            if not post_error:
+                thresholds = PILEUP_THRESHOLDS if pileup is True else tuple(int(x) for x in pileup)
+                write_variants_tsv(index.index, pile.variants(-1, *thresholds),
+                                   os.path.join(mapped_folder if last_index else hits_folder, sample_name + ".variants.tsv"))
+        finally:
+            pile.close()
     if post_error:
         raise post_error[0]
     if not last_index:
@@ -517,6 +543,21 @@ def write_coverage_csv(cov, path):
             out.write("{},{},{},{},{:.6f},{:.6f},{}\n".format(
                 index.genome_names[int(index.contig_genome[rid])], index.contig_names[rid], length, covered,
                 covered / length if length else 0.0, depth_sum / length if length else 0.0, int(row["n_aln"])))
+
+
+def write_variants_tsv(index, variants, path):
+    """One row per called variant (`_capi.VARIANT_DTYPE`, as `Pileup.variants` returns them), appended to `path` (the
+    header when the file is new): genome and contig by name, the 0-based position, reference and alternative allele
+    ('-' a deleted base, '+' an insertion behind `pos`), its count, the records over the base and count * 1000 // span."""
+    new = not os.path.exists(path) or not os.path.getsize(path)
+    with open(path, "a") as out:
+        if new:
+            out.write("\t".join(VARIANTS_TSV_HEADER) + "\n")
+        for v in variants:
+            rid, count, span = int(v["rid"]), int(v["count"]), int(v["span"])
+            out.write("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(
+                index.genome_names[int(index.contig_genome[rid])], index.contig_names[rid], int(v["pos"]), v["ref"].decode(), v["alt"].decode(),
+                count, span, count * 1000 // span if span else 0))
 
 
 def _remove_consumed(sample):

@@ -100,6 +100,10 @@ void launch_export_strings(const Batch &B, bool write, mnc_aln_t *alns, int64_t 
 const mnc_index *coverage_index(const mnc_coverage *cv);
 int coverage_device_of(const mnc_coverage *cv);
 int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream_t st);
+// pileup accumulator (k_pileup.hip)
+const mnc_index *pileup_index(const mnc_pileup *pu);
+int pileup_device_of(const mnc_pileup *pu);
+int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st);
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
@@ -197,7 +201,7 @@ static SharedWs *shared_ws(int device, int add_ref)
 }
 
 // ================================================================ index residency
-int check_device(int device)                                // (k_coverage.hip uses it as well)
+int check_device(int device)                                // (k_coverage.hip and k_pileup.hip use it as well)
 {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible"); return MNC_ERR_NODEVICE; }
@@ -1746,6 +1750,28 @@ extern "C" int mnc_engine_add_coverage(mnc_engine *e, mnc_coverage *cov, int wha
 	if (B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
 	return coverage_add(cov, B, sel, span, e->stream);
+}
+
+// ---------------------------------------------------------------- pileup of the last batch
+// The same for the per-base pileup (k_pileup.hip): one kernel on the engine's stream, every check before the launch.
+extern "C" int mnc_engine_add_pileup(mnc_engine *e, mnc_pileup *pu, int what)
+{
+	if (!e || !pu) return MNC_ERR_ARG;
+	const int sel = what & (MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED);
+	if (what & ~(MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED)) { set_error("`what` (0x%x) holds more than a selector (MNC_COV_SPAN has no meaning for a pileup)", what); return MNC_ERR_ARG; }
+	if (sel == 0 || (sel & (sel - 1))) { set_error("exactly one of MNC_COV_GATED / PRIMARY / ALL / ASSIGNED is required"); return MNC_ERR_ARG; }
+	if (pileup_index(pu) != e->idx || pileup_device_of(pu) != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
+	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
+	if (e->have_merged) {
+		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
+		          "alone -- classify the two groups in separate calls to add their pileup");
+		return MNC_ERR_UNSUPPORTED;
+	}
+	const Batch &B = e->B;
+	if ((B.n_reads ? B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("a pileup needs the CIGARs of MNC_CONTRACT_DP"); return MNC_ERR_ARG; }
+	if (B.n_reads == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return pileup_add(pu, B, sel, e->stream);
 }
 
 // ---------------------------------------------------------------- counters / dumps

@@ -332,11 +332,16 @@ class Aligner:
         """A coverage accumulator (`_capi.Coverage`) for this index on this object's device: pass it to `map_batch`."""
         return _capi.Coverage(self._index, self._device, bin_bases)
 
-    def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED):
+    def pileup(self):
+        """A per-base pileup accumulator (`_capi.Pileup`) for this index on this object's device: pass it to `map_batch`."""
+        return _capi.Pileup(self._index, self._device)
+
+    def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
-        added to it -- `coverage_what`: one `_capi.COV_*` selector, optionally | COV_SPAN -- before the hits are fetched."""
+        added to it -- `coverage_what`: one `_capi.COV_*` selector, optionally | COV_SPAN -- before the hits are fetched; with
+        `pileup` (an accumulator of `pileup()`) likewise, `pileup_what` one selector."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -347,6 +352,8 @@ class Aligner:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
         if coverage is not None:
             eng.add_coverage(coverage, coverage_what)
+        if pileup is not None:
+            eng.add_pileup(pileup, pileup_what)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
