@@ -189,6 +189,12 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *                                                reference base on its left, whatever it inserts
  *   a reference base with 2^31 or more           outside the contract: every plane of mnc_pileup holds int32 per base
  *   observations in one pileup plane             (mnc_pileup_reset starts over)
+ *   abundance after a call that ran both the     mnc_engine_add_abundance: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
+ *   usual and the wide pass                      coverage); a call whose reads are all long adds like any other
+ *   abundance under MNC_CONTRACT_CHAIN           mnc_engine_add_abundance: MNC_ERR_ARG (no dp_max to compare the genomes by)
+ *   a candidate row beyond cap_cands             not stored and counted in n_dropped; mnc_abundance_solve: MNC_ERR_RANGE until
+ *                                                mnc_abundance_reset
+ *   a read that fits more than six genomes       sees six: a region list holds a primary and best_n = 5 secondaries
  */
 
 /* ---------------------------------------------------------------- classify
@@ -562,6 +568,95 @@ int  mnc_pileup_call_variants(mnc_pileup *pu, int rid, int32_t min_depth, int32_
  * among the tied, else the first of them in that order -- written 'A' 'C' 'G' 'T' or '-'.  Insertions do not appear:
  * their bases are not stored. */
 int  mnc_pileup_consensus(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t min_depth, char *out /* end - start */);
+
+/* ---------------------------------------------------------------- abundance
+ * Which of several close genomes is in the sample, and how much of each: the other half of the focus pass' question.  The
+ * count table cannot answer it -- a read counts only with a primary hit of mapq >= min_mapq, and against genomes 0.5-1 %
+ * apart MAPQ drops to single digits on every stretch they share -- but each read's region list already holds its primary
+ * and up to best_n secondaries with a base-level score dp_max each.  An mnc_abundance collects, per read, the genomes that
+ * fit it about equally well, and mnc_abundance_solve runs an expectation-maximisation over those candidate lists (as
+ * Pathoscope and its descendants do on top of an aligner): theta = the share of the sample's reads each genome explains.
+ * It sits beside mnc_coverage and mnc_pileup and has their lifetime rules: it belongs to one index on one device, lives
+ * across classify calls and engines, is added to from the last batch as it stands in HBM (csrc/k_abundance.hip)
+ * asynchronously on the engine's stream with no host wait, and runs only when asked for: a batch that does not ask costs
+ * not one more kernel, allocation or byte.  Threading is mnc_pileup's: engines of the same index and device may add to one
+ * mnc_abundance from their own threads at the same time; reset, add_lists and the read-outs (info, fetch_*, solve) are for
+ * one thread at a time, and not while an engine adds.  A "genome" is the index's: mnc_index_contig_genome, G = n_genomes.
+ *
+ * What one read contributes (mnc_engine_add_abundance).  Take every record of the read's region list that has a CIGAR --
+ * primaries, secondaries, Z-drop splits and inversion regions alike, the set MNC_COV_ALL walks.  For each genome g with at
+ * least one such record, s_g = the largest dp_max of the read's records on contigs of g; best = the largest s_g;
+ * delta_g = best - s_g >= 0.  Genome g is a CANDIDATE of the read iff delta_g <= max_delta.  A read with no record adds
+ * nothing.  A read with exactly one candidate adds 1 to unique[g] (int64) and is not stored.  A read with two or more is
+ * stored as one row of a CSR of (genome, delta) pairs in ascending genome id.  Rows are stored in no particular order --
+ * nothing below depends on it -- and mnc_abundance_fetch_lists returns them SORTED: lexicographically by the row's sequence
+ * genome[0], delta[0], genome[1], delta[1], ...; a row that is a prefix of another comes first.  n_reads counts every read
+ * that added something (to unique or as a stored row).
+ * Capacity: cap_cands candidate slots (12 bytes of HBM each: 4 + 4 and half a row offset).  A row that does not fit is not
+ * stored: it is counted in n_dropped, adds nothing to unique or n_reads, and nothing is written past the end; a later,
+ * shorter row may still fit.  mnc_abundance_solve answers MNC_ERR_RANGE while n_dropped > 0 (reset starts over).
+ * Known limit: the candidates are what the region list holds -- a primary and at most best_n = 5 secondaries (MapParams) --
+ * so a read that fits more than six genomes equally well sees six of them.
+ *
+ * Weights.  scale_q is quarter-bits of likelihood per unit of alignment score: with x = delta * scale_q a candidate weighs
+ *   w = ldexp(T[x & 3], -(x >> 2)),   T[f] = 2^(-f/4) as exactly these doubles:
+ *   0x1.0000000000000p+0, 0x1.ae89f995ad3adp-1, 0x1.6a09e667f3bcdp-1, 0x1.306fe0a31b715p-1
+ * i.e. w = 2^(-x/4).  At the default scale_q = 3 one mismatch (6 units of score at a = 2, b = 4) costs a factor 2^-4.5,
+ * about what a base call of 4-5 % error probability makes of a mismatch; the default is a guess of that kind and has not
+ * been fitted to data.  max_delta * scale_q <= 4000 keeps every weight a normal double.
+ *
+ * mnc_abundance_solve: exact and reproducible -- one defined answer whatever the row order, the launch shape or the number
+ * of batches the reads came in.  Start: theta[g] = 1.0 / G.  One iteration:
+ *   acc[g] = unique[g] * 2^32                                      (uint64)
+ *   for every stored row, candidates j in stored order:
+ *     t_j = w_j * theta[genome_j];  z = t_0 + t_1 + ... added left to right, starting from 0.0
+ *     if z > 0:  p_j = t_j / z;  acc[genome_j] += (uint64) floor(p_j * 4294967296.0)
+ *   total = the sum of acc (uint64, exact);  theta[g] = (double) acc[g] / (double) total   (all zeros if total = 0)
+ * Every multiply, add and divide is one IEEE double operation rounded to nearest, never a fused multiply-add; the two
+ * conversions to double round to nearest.  The run stops after the iteration in which max_g |acc[g] - previous acc[g]| <=
+ * tol_q32, compared as integers -- "previous" of the first iteration is all zeros, so with reads present the test can be met
+ * from the second iteration on -- or after max_iter iterations.  *iters = the iterations run; expected[g] = (double) acc[g] /
+ * 4294967296.0 of the last iteration (reads attributed to g; their sum falls short of the reads by less than 2^-32 per
+ * stored candidate); theta is the last iteration's.  With nothing added theta and expected are zeros and *iters = 0.  The sums
+ * are integer sums, so the M step does not depend on order: no floating-point atomic anywhere.  The accumulator is left as
+ * it is: solve can be called between the batches of a run. */
+typedef struct mnc_abundance mnc_abundance;
+/* MNC_ERR_ARG: cap_cands < 0 (or >= 2^32), max_delta < 0, scale_q < 1, max_delta * scale_q > 4000.  MNC_ERR_NODEVICE without
+ * a gfx950 device, MNC_ERR_NOMEM when HBM is short.  The Python layer's defaults: max_delta = 80, scale_q = 3. */
+int  mnc_abundance_create(mnc_index *idx, int device, int64_t cap_cands, int32_t max_delta, int32_t scale_q, mnc_abundance **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_abundance_free(mnc_abundance *ab);
+/* forgets every read: unique, the stored rows, n_reads and n_dropped; asynchronous */
+int  mnc_abundance_reset(mnc_abundance *ab);
+/* HBM the accumulator holds: 12 bytes per candidate slot and 32 bytes per genome */
+int  mnc_abundance_device_bytes(const mnc_abundance *ab, int64_t *bytes);
+/* Adds the last classified batch of `eng` as it stands in HBM.  Needs no mnc_engine_export_alignments and disturbs none.
+ * Asynchronous on the engine's stream, no host wait.  MNC_ERR_ARG: `ab` is for another index or device than the engine's
+ * current ones; no batch has been classified yet; MNC_CONTRACT_CHAIN (no dp_max).  MNC_ERR_UNSUPPORTED: the last call ran
+ * both the usual and the wide pass (the engine holds the wide pass alone); a call whose reads are all long adds like any
+ * other.  MNC_ERR_NODEVICE / MNC_ERR_NOMEM as elsewhere.  The accumulator is untouched on any error. */
+int  mnc_engine_add_abundance(mnc_engine *eng, mnc_abundance *ab);
+/* Adds rows made by the caller -- row r = (genome, delta)[offsets[r] .. offsets[r + 1]) -- with the same treatment: a row of
+ * one candidate goes to unique, a row of two or more is stored; n_reads grows by n_reads.  For a caller who merges the
+ * parts of a multi-part database itself (that needs read identity, which the library does not carry here).  Checked on the
+ * host before anything is touched: MNC_ERR_ARG for an empty row, genome ids not strictly ascending within a row, a genome
+ * id >= G or negative, a delta negative or above max_delta; MNC_ERR_RANGE when the rows would not fit -- nothing is added
+ * then and n_dropped stays as it was.  Waits for the work queued so far. */
+int  mnc_abundance_add_lists(mnc_abundance *ab, int64_t n_reads, const int64_t *offsets, const int32_t *genome, const int32_t *delta);
+/* the counts as they stand (waits for the work queued so far); any pointer may be NULL.  n_stored_reads = rows of the CSR,
+ * n_cands = candidate slots taken */
+int  mnc_abundance_info(mnc_abundance *ab, int64_t *n_reads, int64_t *n_stored_reads, int64_t *n_cands, int64_t *n_dropped);
+int  mnc_abundance_fetch_unique(mnc_abundance *ab, int64_t *unique /* [G] */);
+/* the stored rows, sorted as stated above: offsets[n_stored_reads + 1] (offsets[0] = 0), genome / delta [n_cands].
+ * MNC_ERR_RANGE, nothing written, when cap_reads < n_stored_reads or cap_cands < n_cands (mnc_abundance_info has both) */
+int  mnc_abundance_fetch_lists(mnc_abundance *ab, int64_t *offsets, int32_t *genome, int32_t *delta, int64_t cap_reads, int64_t cap_cands);
+/* the EM above.  MNC_ERR_ARG for max_iter < 1; MNC_ERR_RANGE while n_dropped > 0.  Queues every iteration without reading
+ * anything back (a word on the device turns the launches behind the stop into no-ops) and waits once at the end. */
+int  mnc_abundance_solve(mnc_abundance *ab, int32_t max_iter, uint64_t tol_q32, double *theta /* [G] */, double *expected /* [G] */, int32_t *iters);
+/* The accumulator in place (device pointers; any out pointer may be NULL): unique int64[G]; the CSR as stored (NOT sorted):
+ * d_offsets int64[n_stored_reads + 1], d_genome / d_delta int32[n_cands].  Ordered behind the adds only after a read-out
+ * call above or a sync of the engines that added. */
+int  mnc_abundance_device(mnc_abundance *ab, const int64_t **d_unique, const int64_t **d_offsets, const int32_t **d_genome, const int32_t **d_delta);
 
 /* ---------------------------------------------------------------- FASTQ batches and read routing
  * Replaces the per-record Biopython objects of the reference's loop:

@@ -86,6 +86,9 @@ EXPORTS = [
     "mnc_coverage_summary", "mnc_coverage_fetch_bins", "mnc_coverage_fetch_depth", "mnc_coverage_device",
     "mnc_pileup_create", "mnc_pileup_free", "mnc_pileup_reset", "mnc_pileup_device_bytes", "mnc_pileup_device", "mnc_engine_add_pileup",
     "mnc_pileup_fetch_counts", "mnc_pileup_call_variants", "mnc_pileup_consensus",
+    "mnc_abundance_create", "mnc_abundance_free", "mnc_abundance_reset", "mnc_abundance_device_bytes", "mnc_engine_add_abundance",
+    "mnc_abundance_add_lists", "mnc_abundance_info", "mnc_abundance_fetch_unique", "mnc_abundance_fetch_lists", "mnc_abundance_solve",
+    "mnc_abundance_device",
 ]
 
 
@@ -235,6 +238,17 @@ def lib():
     sig("mnc_pileup_fetch_counts", i32, [vp, i32, i64, i64, vp])
     sig("mnc_pileup_call_variants", i32, [vp, i32, i32, i32, i32, vp, i64, C.POINTER(i64)])
     sig("mnc_pileup_consensus", i32, [vp, i32, i64, i64, i32, vp])
+    sig("mnc_abundance_create", i32, [vp, i32, i64, C.c_int32, C.c_int32, pp])
+    sig("mnc_abundance_free", None, [vp])
+    sig("mnc_abundance_reset", i32, [vp])
+    sig("mnc_abundance_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_engine_add_abundance", i32, [vp, vp])
+    sig("mnc_abundance_add_lists", i32, [vp, i64, vp, vp, vp])
+    sig("mnc_abundance_info", i32, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)])
+    sig("mnc_abundance_fetch_unique", i32, [vp, vp])
+    sig("mnc_abundance_fetch_lists", i32, [vp, vp, vp, vp, i64, i64])
+    sig("mnc_abundance_solve", i32, [vp, C.c_int32, u64, vp, vp, C.POINTER(C.c_int32)])
+    sig("mnc_abundance_device", i32, [vp, pp, pp, pp, pp])
     _LIB = L
     return L
 
@@ -572,6 +586,11 @@ class Engine:
         `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
         check(lib().mnc_engine_add_pileup(self._h, pileup._h if pileup is not None else None, int(what)))
 
+    def add_abundance(self, abundance):
+        """`mnc_engine_add_abundance`: add the candidate genomes of every read of the last classified batch, as it stands in
+        HBM, to the accumulator `abundance`.  Asynchronous."""
+        check(lib().mnc_engine_add_abundance(self._h, abundance._h if abundance is not None else None))
+
     def set_profiling(self, on=True):
         check(lib().mnc_engine_set_profiling(self._h, 1 if on else 0))
 
@@ -763,6 +782,103 @@ class Pileup:
     def close(self):
         if getattr(self, "_h", None):
             lib().mnc_pileup_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------------- abundance
+# Abundance(): the defaults of the Python layer (include/monica_amd.h, "abundance": the weights)
+ABUNDANCE_MAX_DELTA, ABUNDANCE_SCALE_Q = 80, 3
+ABUNDANCE_CAP_CANDS = 1 << 22           # candidate slots when the caller names none: 48 MiB of HBM
+ABUNDANCE_TOL_Q32 = 1 << 22             # solve(): stop once no genome's expected reads move by more than 2^-10 of a read
+ABUNDANCE_MAX_PRODUCT = 4000            # max_delta * scale_q at most: every weight a normal double
+
+
+class Abundance:
+    """Owner of an ``mnc_abundance``: per read the genomes that fit it about as well as its best one, accumulated from
+    batch to batch by `Engine.add_abundance`, and the EM over them (include/monica_amd.h, "abundance")."""
+
+    def __init__(self, index, device=0, cap_cands=ABUNDANCE_CAP_CANDS, max_delta=ABUNDANCE_MAX_DELTA, scale_q=ABUNDANCE_SCALE_Q):
+        cap_cands, max_delta, scale_q = int(cap_cands), int(max_delta), int(scale_q)
+        if cap_cands < 0:
+            raise ValueError(f"cap_cands = {cap_cands}: a number of candidate slots")
+        if max_delta < 0 or scale_q < 1 or max_delta * scale_q > ABUNDANCE_MAX_PRODUCT:
+            raise ValueError(f"max_delta = {max_delta}, scale_q = {scale_q}: max_delta >= 0, scale_q >= 1 and "
+                             f"max_delta * scale_q <= {ABUNDANCE_MAX_PRODUCT} are required")
+        self.index = index
+        self.device = device
+        self.cap_cands, self.max_delta, self.scale_q = cap_cands, max_delta, scale_q
+        self.n_genomes = len(index.genome_names) if index is not None else 0
+        h = C.c_void_p()
+        check(lib().mnc_abundance_create(index._h if index is not None else None, int(device), cap_cands, max_delta, scale_q, C.byref(h)))
+        self._h = h
+
+    def reset(self):
+        check(lib().mnc_abundance_reset(self._h))
+
+    def device_bytes(self):
+        n = C.c_int64(0)
+        check(lib().mnc_abundance_device_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    def add_lists(self, offsets, genome, delta):
+        """Rows made by the caller: row r is (genome, delta)[offsets[r]:offsets[r + 1]], genome ids ascending.  A row of one
+        candidate counts as a unique read, a longer one is stored."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        genome = np.ascontiguousarray(genome, dtype=np.int32)
+        delta = np.ascontiguousarray(delta, dtype=np.int32)
+        if offsets.ndim != 1 or len(offsets) < 1 or len(genome) != len(delta) or (len(offsets) > 1 and int(offsets[-1]) > len(genome)):
+            raise ValueError("offsets holds n_reads + 1 entries into genome / delta, which have one length")
+        check(lib().mnc_abundance_add_lists(self._h, len(offsets) - 1, offsets.ctypes.data, genome.ctypes.data if len(genome) else None,
+                                            delta.ctypes.data if len(delta) else None))
+
+    def info(self):
+        """{"n_reads", "n_stored_reads", "n_cands", "n_dropped"} as they stand (waits for the adds queued so far)."""
+        v = [C.c_int64(0) for _ in range(4)]
+        check(lib().mnc_abundance_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_reads", "n_stored_reads", "n_cands", "n_dropped"), (int(x.value) for x in v)))
+
+    def unique(self):
+        """int64[G]: the reads with exactly one candidate genome."""
+        out = np.zeros(self.n_genomes, dtype=np.int64)
+        check(lib().mnc_abundance_fetch_unique(self._h, out.ctypes.data if len(out) else None))
+        return out
+
+    def lists(self):
+        """The stored rows, sorted lexicographically by their (genome, delta) sequence: (offsets int64[n + 1], genome
+        int32, delta int32)."""
+        inf = self.info()
+        off = np.zeros(inf["n_stored_reads"] + 1, dtype=np.int64)
+        gen = np.zeros(inf["n_cands"], dtype=np.int32)
+        dlt = np.zeros(inf["n_cands"], dtype=np.int32)
+        check(lib().mnc_abundance_fetch_lists(self._h, off.ctypes.data, gen.ctypes.data if len(gen) else None, dlt.ctypes.data if len(dlt) else None,
+                                              len(off) - 1, len(gen)))
+        return off, gen, dlt
+
+    def solve(self, max_iter=200, tol_q32=ABUNDANCE_TOL_Q32):
+        """The EM: (theta float64[G], expected reads float64[G], iterations run).  Exact and reproducible; MncError
+        (ERR_RANGE) while rows have been dropped."""
+        theta = np.zeros(self.n_genomes, dtype=np.float64)
+        expected = np.zeros(self.n_genomes, dtype=np.float64)
+        iters = C.c_int32(0)
+        check(lib().mnc_abundance_solve(self._h, int(max_iter), int(tol_q32), theta.ctypes.data if len(theta) else None,
+                                        expected.ctypes.data if len(expected) else None, C.byref(iters)))
+        return theta, expected, int(iters.value)
+
+    def device_arrays(self):
+        """Device addresses (ints) of unique, the CSR's offsets, genome and delta as stored: `mnc_abundance_device`."""
+        p = [C.c_void_p() for _ in range(4)]
+        check(lib().mnc_abundance_device(self._h, *[C.byref(x) for x in p]))
+        return tuple(int(x.value or 0) for x in p)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mnc_abundance_free(self._h)
             self._h = None
 
     def __del__(self):

@@ -69,6 +69,11 @@ COVERAGE_CSV_HEADER = ("genome", "contig", "length", "covered_bases", "breadth",
 # `pileup=True`: (min_depth, min_count, min_permille) of the sample's variant calls; a 3-tuple in its place sets its own
 PILEUP_THRESHOLDS = (5, 3, 500)
 VARIANTS_TSV_HEADER = ("genome", "contig", "pos", "ref", "alt", "count", "span", "permille")
+# `abundance=True`: the accumulator's defaults (`_capi.Abundance`); a dict of cap_cands / max_delta / scale_q / max_iter /
+# tol_q32 in its place sets its own
+ABUNDANCE_CSV_HEADER = ("genome", "theta", "expected_reads", "unique_reads")
+ABUNDANCE_MULTI_PART = ("abundance= needs a database of ONE index part: a read's candidate genomes would have to be merged across "
+                        "the parts, which needs read identity -- merge them yourself and hand the rows to Abundance.add_lists")
 DEFAULT_MAX_WORKERS = int(os.environ.get("MONICA_AMD_MAX_WORKERS", "8"))   # `n_threads=None`: at most this many samples in flight
 TIMINGS = {}                      # per sample name: seconds spent per phase of aligner() (diagnostics)
 PIPE_TRACE = [] if os.environ.get("MONICA_AMD_PIPE_TRACE") else None   # (stage, reads, start, end) per batch and stage (diagnostics)
@@ -127,10 +132,12 @@ def index_loader(index_file):
 def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quality=60, overnight=False, n_threads=None,
                            focus_species=[], output_folder=None, mapped_files_folder=MAPPED_FILES_FOLDER,
                            unmapped_files_folder=UNMAPPED_FILES_FOLDER, ambiguous_files_folder=AMBIGUOUS_FILES_FOLDER,
-                           hits_files_folder=HITS_FILES_FOLDER, focus_file_folder=FOCUS_FILES_FOLDER, coverage=None, pileup=None):
+                           hits_files_folder=HITS_FILES_FOLDER, focus_file_folder=FOCUS_FILES_FOLDER, abundance=None, coverage=None, pileup=None):
     """Classify every non-empty `*fastq` file of `query_folder` against the index parts
     (aligner.py:65-111): every part but the last only collects hits; the last part decides.
-    `coverage`, `pileup` (not in the reference; off by default): see `aligner_coverage`."""
+    `abundance`, `coverage`, `pileup` (not in the reference; off by default): see `aligner_coverage`."""
+    if abundance and len(indexes_paths) != 1:
+        raise ValueError(ABUNDANCE_MULTI_PART)
     os.chdir(query_folder)
     samples = [f for f in os.listdir(".") if f.endswith("fastq") and os.stat(f).st_size]
     if not samples:
@@ -157,7 +164,7 @@ def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quali
     pool = ThreadPool(workers)
     rep = itertools.repeat
     mappy.reserve_index_cache(len(indexes_paths))
-    extra = [rep(coverage), rep(pileup)] if coverage or pileup else []     # the arguments `aligner` does not have
+    extra = [rep(abundance), rep(coverage), rep(pileup)] if abundance or coverage or pileup else []     # the arguments `aligner` does not have
     try:
         for part in indexes_paths[:-1]:
             index = index_loader(part)
@@ -193,10 +200,16 @@ def aligner(sample, sample_name, index, mode=None, hits_folder=None, mapping_qua
 
 def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, mapping_quality=None, overnight=False,
                      focus_species=[], mapped_folder=None, unmapped_folder=None, ambiguous_folder=None, focus_folder=None,
-                     last_index=False, coverage=None, pileup=None):
-    """One sample file against one index part (aligner.py:179-279): `aligner` and the opt-in `coverage=` and `pileup=`
-    arguments, which the reference does not have (`aligner` itself keeps the reference's parameter list;
-    `multi_threaded_aligner(..., coverage=, pileup=)` calls this one).
+                     last_index=False, abundance=None, coverage=None, pileup=None):
+    """One sample file against one index part (aligner.py:179-279): `aligner` and the opt-in `abundance=`, `coverage=` and
+    `pileup=` arguments, which the reference does not have (`aligner` itself keeps the reference's parameter list;
+    `multi_threaded_aligner(..., abundance=, coverage=, pileup=)` calls this one).
+
+    `abundance` (None / False: off, and nothing changes -- same outputs, same files): True, or a dict with any of
+    cap_cands / max_delta / scale_q (`mappy_compat.Aligner.abundance`) and max_iter / tol_q32 (`Abundance.solve`), collects
+    every read's candidate genomes from every batch, solves the EM at the end of the sample and leaves
+    `<sample_name>.abundance.csv` (`ABUNDANCE_CSV_HEADER`, one row per genome) beside the routed files.  Only for a
+    database of one index part: with carried hits or a part that is not the last, ValueError before anything runs.
 
     `coverage` (None / False: off, and nothing changes -- same outputs, same files): True, or the
     bin width in bases, makes a device accumulator for this sample and index part (`mappy_compat.Aligner.coverage`),
@@ -223,6 +236,8 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     if mapping_quality is None:
         raise TypeError("'>=' not supported between instances of 'int' and 'NoneType'")
     carried_file = os.path.join(hits_folder, sample_name + "_hits.pkl")
+    if abundance and (not last_index or os.path.exists(carried_file)):
+        raise ValueError(ABUNDANCE_MULTI_PART)
     sample_hits = _capi.HitMap(carried_file if os.path.exists(carried_file) else None)
     t_engine = time.perf_counter()
     engine = index.engine()
@@ -235,6 +250,8 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
         cov = index.coverage(COVERAGE_BIN_BASES if coverage is True else int(coverage))
         cov_what = _capi.COV_ASSIGNED if last_index and not os.path.exists(carried_file) else _capi.COV_GATED
     pile = index.pileup() if pileup else None
+    ab_opts = dict(abundance) if isinstance(abundance, dict) else {}
+    abund = index.abundance(**{k: v for k, v in ab_opts.items() if k in ("cap_cands", "max_delta", "scale_q")}) if abundance else None
 
     clock = TIMINGS.setdefault(sample_name, dict.fromkeys(("parse", "classify", "carry", "route", "count", "engine", "open", "close", "remove"), 0.0))
     clock["engine"] += t_engine
@@ -352,6 +369,13 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
                 if err.code != _capi.ERR_UNSUPPORTED:
                     raise
                 print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no pileup")
+        if abund is not None:
+            try:
+                engine.add_abundance(abund)                   # asynchronous likewise
+            except _capi.MncError as err:
+                if err.code != _capi.ERR_UNSUPPORTED:
+                    raise
+                print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no abundance candidates")
         clock["classify"] += time.perf_counter() - t1
         _trace("classify", batch.n, t1)
         n_skipped = int((out[0] == _capi.SKIPPED).sum())
@@ -506,6 +530,13 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
                                    os.path.join(mapped_folder if last_index else hits_folder, sample_name + ".variants.tsv"))
         finally:
             pile.close()
+    if abund is not None:
+        try:
+            if not post_error:
+                write_abundance_csv(abund, os.path.join(mapped_folder, sample_name + ".abundance.csv"),
+                                    **{k: v for k, v in ab_opts.items() if k in ("max_iter", "tol_q32")})
+        finally:
+            abund.close()
     if post_error:
         raise post_error[0]
     if not last_index:
@@ -543,6 +574,18 @@ def write_coverage_csv(cov, path):
             out.write("{},{},{},{},{:.6f},{:.6f},{}\n".format(
                 index.genome_names[int(index.contig_genome[rid])], index.contig_names[rid], length, covered,
                 covered / length if length else 0.0, depth_sum / length if length else 0.0, int(row["n_aln"])))
+
+
+def write_abundance_csv(abund, path, **solve_args):
+    """One row per genome of the accumulator's index, written to `path`: the EM's share of the sample (`theta`), the reads
+    it attributes to the genome and the reads that had no other candidate.  The floats are written with `repr`, so they
+    read back as the doubles `Abundance.solve` returned."""
+    theta, expected, _ = abund.solve(**solve_args)
+    unique = abund.unique()
+    with open(path, "w") as out:
+        out.write(",".join(ABUNDANCE_CSV_HEADER) + "\n")
+        for g, name in enumerate(abund.index.genome_names):
+            out.write("{},{!r},{!r},{}\n".format(name, float(theta[g]), float(expected[g]), int(unique[g])))
 
 
 def write_variants_tsv(index, variants, path):

@@ -104,6 +104,10 @@ int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream
 const mnc_index *pileup_index(const mnc_pileup *pu);
 int pileup_device_of(const mnc_pileup *pu);
 int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st);
+// abundance accumulator (k_abundance.hip)
+const mnc_index *abundance_index(const mnc_abundance *ab);
+int abundance_device_of(const mnc_abundance *ab);
+int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st);
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
@@ -201,7 +205,7 @@ static SharedWs *shared_ws(int device, int add_ref)
 }
 
 // ================================================================ index residency
-int check_device(int device)                                // (k_coverage.hip and k_pileup.hip use it as well)
+int check_device(int device)                                // (k_coverage.hip, k_pileup.hip and k_abundance.hip use it as well)
 {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible"); return MNC_ERR_NODEVICE; }
@@ -1772,6 +1776,25 @@ extern "C" int mnc_engine_add_pileup(mnc_engine *e, mnc_pileup *pu, int what)
 	if (B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
 	return pileup_add(pu, B, sel, e->stream);
+}
+
+// ---------------------------------------------------------------- abundance candidates of the last batch
+// The same for the EM's candidate lists (k_abundance.hip): every record with a CIGAR, as MNC_COV_ALL walks them.
+extern "C" int mnc_engine_add_abundance(mnc_engine *e, mnc_abundance *ab)
+{
+	if (!e || !ab) return MNC_ERR_ARG;
+	if (abundance_index(ab) != e->idx || abundance_device_of(ab) != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
+	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
+	if (e->have_merged) {
+		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
+		          "alone -- classify the two groups in separate calls to add their abundance candidates");
+		return MNC_ERR_UNSUPPORTED;
+	}
+	const Batch &B = e->B;
+	if ((B.n_reads ? B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("abundance candidates need the dp_max of MNC_CONTRACT_DP"); return MNC_ERR_ARG; }
+	if (B.n_reads == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return abundance_add(ab, B, e->stream);
 }
 
 // ---------------------------------------------------------------- counters / dumps

@@ -336,12 +336,19 @@ class Aligner:
         """A per-base pileup accumulator (`_capi.Pileup`) for this index on this object's device: pass it to `map_batch`."""
         return _capi.Pileup(self._index, self._device)
 
-    def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED):
+    def abundance(self, cap_cands=_capi.ABUNDANCE_CAP_CANDS, max_delta=_capi.ABUNDANCE_MAX_DELTA, scale_q=_capi.ABUNDANCE_SCALE_Q):
+        """An abundance accumulator (`_capi.Abundance`) for this index on this object's device: pass it to `map_batch`,
+        then `solve()` it."""
+        return _capi.Abundance(self._index, self._device, cap_cands, max_delta, scale_q)
+
+    def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
+                  abundance=None):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
         added to it -- `coverage_what`: one `_capi.COV_*` selector, optionally | COV_SPAN -- before the hits are fetched; with
-        `pileup` (an accumulator of `pileup()`) likewise, `pileup_what` one selector."""
+        `pileup` (an accumulator of `pileup()`) likewise, `pileup_what` one selector; with `abundance` (an accumulator of
+        `abundance()`) every read's candidate genomes are added to it."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -354,6 +361,8 @@ class Aligner:
             eng.add_coverage(coverage, coverage_what)
         if pileup is not None:
             eng.add_pileup(pileup, pileup_what)
+        if abundance is not None:
+            eng.add_abundance(abundance)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
