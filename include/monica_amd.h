@@ -417,7 +417,8 @@ int mnc_index_getseq(const mnc_index *idx, int rid, int64_t start, int64_t end, 
  *
  * An mnc_coverage belongs to one index on one device and holds a depth track over every reference base of that index.  It
  * is additive: adding batch A and then batch B equals adding one batch with the reads of both; it lives across any number
- * of classify calls and across engines of the same index and device.  One thread at a time, like an engine.
+ * of classify calls and across engines of the same index and device.  Engines of the same index and device may add to one
+ * mnc_coverage from their own threads at the same time; reset and the read-outs are for one thread at a time.
  *
  * What a call adds -- `what` = exactly ONE selector, optionally | MNC_COV_SPAN:
  *   MNC_COV_GATED     every record that passes the gate of the call (primary and mapq >= min_mapq: mnc_aln_t.flags bit 1)

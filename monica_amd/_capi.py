@@ -579,17 +579,20 @@ class Engine:
     def add_coverage(self, cov, what=COV_ASSIGNED):
         """`mnc_engine_add_coverage`: add the last classified batch, as it stands in HBM, to the accumulator `cov`.
         `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED, optionally | COV_SPAN.  Asynchronous."""
-        check(lib().mnc_engine_add_coverage(self._h, cov._h if cov is not None else None, int(what)))
+        self._add("mnc_engine_add_coverage", cov, int(what))
 
     def add_pileup(self, pileup, what=COV_GATED):
         """`mnc_engine_add_pileup`: add the last classified batch, as it stands in HBM, to the accumulator `pileup`.
         `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
-        check(lib().mnc_engine_add_pileup(self._h, pileup._h if pileup is not None else None, int(what)))
+        self._add("mnc_engine_add_pileup", pileup, int(what))
 
     def add_abundance(self, abundance):
         """`mnc_engine_add_abundance`: add the candidate genomes of every read of the last classified batch, as it stands in
         HBM, to the accumulator `abundance`.  Asynchronous."""
-        check(lib().mnc_engine_add_abundance(self._h, abundance._h if abundance is not None else None))
+        self._add("mnc_engine_add_abundance", abundance)
+
+    def _add(self, symbol, acc, *args):
+        check(getattr(lib(), symbol)(self._h, acc._h if acc is not None else None, *args))
 
     def set_profiling(self, on=True):
         check(lib().mnc_engine_set_profiling(self._h, 1 if on else 0))
@@ -655,26 +658,49 @@ class Engine:
         return buf[:n.value].view(dtype).copy()
 
 
+# ---------------------------------------------------------------------------------- the accumulators
+class _Accumulator:
+    """What the owners of the accumulator handles share: ``mnc_<_c>_create`` / ``_reset`` / ``_device_bytes`` / ``_free``."""
+
+    _c = None                                                   # "coverage", "pileup", "abundance"
+
+    def _create(self, index, device, *args):
+        h = C.c_void_p()
+        check(getattr(lib(), f"mnc_{self._c}_create")(index._h if index is not None else None, int(device), *args, C.byref(h)))
+        self._h = h
+
+    def reset(self):
+        check(getattr(lib(), f"mnc_{self._c}_reset")(self._h))
+
+    def device_bytes(self):
+        n = C.c_int64(0)
+        check(getattr(lib(), f"mnc_{self._c}_device_bytes")(self._h, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), f"mnc_{self._c}_free")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---------------------------------------------------------------------------------- coverage
-class Coverage:
+class Coverage(_Accumulator):
     """Owner of an ``mnc_coverage``: depth of coverage over every reference base of one index on one device, accumulated
     from batch to batch by `Engine.add_coverage` (include/monica_amd.h, "coverage")."""
+
+    _c = "coverage"
 
     def __init__(self, index, device=0, bin_bases=1024):
         self.index = index
         self.device = device
         self.bin_bases = int(bin_bases)
-        h = C.c_void_p()
-        check(lib().mnc_coverage_create(index._h if index is not None else None, int(device), self.bin_bases, C.byref(h)))
-        self._h = h
-
-    def reset(self):
-        check(lib().mnc_coverage_reset(self._h))
-
-    def device_bytes(self):
-        n = C.c_int64(0)
-        check(lib().mnc_coverage_device_bytes(self._h, C.byref(n)))
-        return int(n.value)
+        self._create(index, device, self.bin_bases)
 
     def summary(self):
         """One row per contig (COV_SUMMARY_DTYPE): covered bases, depth sum, maximal depth, records added.  Waits for the
@@ -711,38 +737,19 @@ class Coverage:
         check(lib().mnc_coverage_device(self._h, C.byref(p), C.byref(n)))
         return int(p.value or 0), int(n.value)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mnc_coverage_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---------------------------------------------------------------------------------- pileup
-class Pileup:
+class Pileup(_Accumulator):
     """Owner of an ``mnc_pileup``: what the reads say at every reference base of one index on one device -- depth, the
     counts of A C G T N, deletions and insertions -- accumulated from batch to batch by `Engine.add_pileup`
     (include/monica_amd.h, "pileup")."""
 
+    _c = "pileup"
+
     def __init__(self, index, device=0):
         self.index = index
         self._device = device                                   # (`device` is the method below)
-        h = C.c_void_p()
-        check(lib().mnc_pileup_create(index._h if index is not None else None, int(device), C.byref(h)))
-        self._h = h
-
-    def reset(self):
-        check(lib().mnc_pileup_reset(self._h))
-
-    def device_bytes(self):
-        n = C.c_int64(0)
-        check(lib().mnc_pileup_device_bytes(self._h, C.byref(n)))
-        return int(n.value)
+        self._create(index, device)
 
     def _end(self, rid, end):
         return (self.index.contig_lens[rid] if 0 <= rid < len(self.index.contig_lens) else 0) if end is None else int(end)
@@ -779,17 +786,6 @@ class Pileup:
         check(lib().mnc_pileup_device(self._h, C.byref(d), C.byref(a), C.byref(n)))
         return int(d.value or 0), int(a.value or 0), int(n.value)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mnc_pileup_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---------------------------------------------------------------------------------- abundance
 # Abundance(): the defaults of the Python layer (include/monica_amd.h, "abundance": the weights)
@@ -799,9 +795,11 @@ ABUNDANCE_TOL_Q32 = 1 << 22             # solve(): stop once no genome's expecte
 ABUNDANCE_MAX_PRODUCT = 4000            # max_delta * scale_q at most: every weight a normal double
 
 
-class Abundance:
+class Abundance(_Accumulator):
     """Owner of an ``mnc_abundance``: per read the genomes that fit it about as well as its best one, accumulated from
     batch to batch by `Engine.add_abundance`, and the EM over them (include/monica_amd.h, "abundance")."""
+
+    _c = "abundance"
 
     def __init__(self, index, device=0, cap_cands=ABUNDANCE_CAP_CANDS, max_delta=ABUNDANCE_MAX_DELTA, scale_q=ABUNDANCE_SCALE_Q):
         cap_cands, max_delta, scale_q = int(cap_cands), int(max_delta), int(scale_q)
@@ -814,17 +812,7 @@ class Abundance:
         self.device = device
         self.cap_cands, self.max_delta, self.scale_q = cap_cands, max_delta, scale_q
         self.n_genomes = len(index.genome_names) if index is not None else 0
-        h = C.c_void_p()
-        check(lib().mnc_abundance_create(index._h if index is not None else None, int(device), cap_cands, max_delta, scale_q, C.byref(h)))
-        self._h = h
-
-    def reset(self):
-        check(lib().mnc_abundance_reset(self._h))
-
-    def device_bytes(self):
-        n = C.c_int64(0)
-        check(lib().mnc_abundance_device_bytes(self._h, C.byref(n)))
-        return int(n.value)
+        self._create(index, device, cap_cands, max_delta, scale_q)
 
     def add_lists(self, offsets, genome, delta):
         """Rows made by the caller: row r is (genome, delta)[offsets[r]:offsets[r + 1]], genome ids ascending.  A row of one
@@ -875,17 +863,6 @@ class Abundance:
         p = [C.c_void_p() for _ in range(4)]
         check(lib().mnc_abundance_device(self._h, *[C.byref(x) for x in p]))
         return tuple(int(x.value or 0) for x in p)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().mnc_abundance_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------------- host helpers

@@ -252,6 +252,11 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     pile = index.pileup() if pileup else None
     ab_opts = dict(abundance) if isinstance(abundance, dict) else {}
     abund = index.abundance(**{k: v for k, v in ab_opts.items() if k in ("cap_cands", "max_delta", "scale_q")}) if abundance else None
+    # what every classified batch is added to (asynchronously, behind the batch's kernels), and what a message calls it
+    adds = [(add, noun) for accum, add, noun in (
+        (cov, lambda: engine.add_coverage(cov, cov_what), "coverage"),
+        (pile, lambda: engine.add_pileup(pile, _capi.COV_GATED), "pileup"),
+        (abund, lambda: engine.add_abundance(abund), "abundance candidates")) if accum is not None]
 
     clock = TIMINGS.setdefault(sample_name, dict.fromkeys(("parse", "classify", "carry", "route", "count", "engine", "open", "close", "remove"), 0.0))
     clock["engine"] += t_engine
@@ -355,27 +360,13 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
                 raise
             mappy.release_idle(index.index)
             out = engine.classify_ptr(batch.bases_ptr, batch.offsets_ptr, batch.n, mapping_quality)
-        if cov is not None:
+        for add, noun in adds:
             try:
-                engine.add_coverage(cov, cov_what)            # asynchronous, behind the batch's kernels
+                add()
             except _capi.MncError as err:
                 if err.code != _capi.ERR_UNSUPPORTED:
                     raise
-                print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no coverage")
-        if pile is not None:
-            try:
-                engine.add_pileup(pile, _capi.COV_GATED)      # asynchronous likewise
-            except _capi.MncError as err:
-                if err.code != _capi.ERR_UNSUPPORTED:
-                    raise
-                print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no pileup")
-        if abund is not None:
-            try:
-                engine.add_abundance(abund)                   # asynchronous likewise
-            except _capi.MncError as err:
-                if err.code != _capi.ERR_UNSUPPORTED:
-                    raise
-                print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no abundance candidates")
+                print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no {noun}")
         clock["classify"] += time.perf_counter() - t1
         _trace("classify", batch.n, t1)
         n_skipped = int((out[0] == _capi.SKIPPED).sum())
@@ -516,27 +507,28 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
         reader.close()
         clock["close"] += time.perf_counter() - t0
     _trace("closed", 0, time.perf_counter())
-    if cov is not None:
-        try:
+    out_folder = mapped_folder if last_index else hits_folder
+
+    def write_coverage():
+        write_coverage_csv(cov, os.path.join(out_folder, sample_name + ".coverage.csv"))
+
+    def write_variants():
+        thresholds = PILEUP_THRESHOLDS if pileup is True else tuple(int(x) for x in pileup)
+        write_variants_tsv(index.index, pile.variants(-1, *thresholds), os.path.join(out_folder, sample_name + ".variants.tsv"))
+
+    def write_abundance():
+        write_abundance_csv(abund, os.path.join(mapped_folder, sample_name + ".abundance.csv"),
+                            **{k: v for k, v in ab_opts.items() if k in ("max_iter", "tol_q32")})
+
+    outputs = [(a, write) for a, write in ((cov, write_coverage), (pile, write_variants), (abund, write_abundance)) if a is not None]
+    try:
+        for accum, write in outputs:
             if not post_error:
-                write_coverage_csv(cov, os.path.join(mapped_folder if last_index else hits_folder, sample_name + ".coverage.csv"))
-        finally:
-            cov.close()
-    if pile is not None:
-        try:
-            if not post_error:
-                thresholds = PILEUP_THRESHOLDS if pileup is True else tuple(int(x) for x in pileup)
-                write_variants_tsv(index.index, pile.variants(-1, *thresholds),
-                                   os.path.join(mapped_folder if last_index else hits_folder, sample_name + ".variants.tsv"))
-        finally:
-            pile.close()
-    if abund is not None:
-        try:
-            if not post_error:
-                write_abundance_csv(abund, os.path.join(mapped_folder, sample_name + ".abundance.csv"),
-                                    **{k: v for k, v in ab_opts.items() if k in ("max_iter", "tol_q32")})
-        finally:
-            abund.close()
+                write()
+            accum.close()                                 # its device memory goes before the next one is read out
+    finally:
+        for accum, _ in outputs:                          # (after an error in a writer: the rest; close() twice is harmless)
+            accum.close()
     if post_error:
         raise post_error[0]
     if not last_index:

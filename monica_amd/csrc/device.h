@@ -288,6 +288,18 @@ __device__ __forceinline__ uint32_t hash30(uint32_t key)
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
+// a read's base as a letter -> 0 .. 3 for A C G T / U in either case, 4 for anything else
+__device__ __forceinline__ int base_nt4(uint8_t c)
+{
+	switch (c) {
+	case 'A': case 'a': return 0;
+	case 'C': case 'c': return 1;
+	case 'G': case 'g': return 2;
+	case 'T': case 't': case 'U': case 'u': return 3;
+	default: return 4;
+	}
+}
+
 // First region slot of a read (regs, regdp, regx, ... are indexed by it; chains_tmp / chain_dst keep anchors / 3).
 // A chain needs three anchors, so a read's chains fit anchors / 3 slots -- but a Z-drop split peels a head of as little
 // as one anchor off a region, and an inversion region has no anchors at all: every read gets slot_pad more, and a read

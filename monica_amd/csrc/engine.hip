@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "scan.h"
+#include "accum.h"
 
 namespace mnc {
 
@@ -96,22 +97,13 @@ void launch_export_records(const Batch &B, const int64_t *aln_off, mnc_aln_t *al
 void launch_export_scan(const mnc_aln_t *alns, int64_t n_aln, int field, int64_t *out, int64_t *sums, hipStream_t st);
 void launch_export_strings(const Batch &B, bool write, mnc_aln_t *alns, int64_t n_aln, const int64_t *cig_off, const int64_t *cs_off,
                            const int64_t *md_off, uint32_t *cigar, char *cs, char *md, int what, hipStream_t st);
-// coverage accumulator (k_coverage.hip)
-const mnc_index *coverage_index(const mnc_coverage *cv);
-int coverage_device_of(const mnc_coverage *cv);
+// the accumulators (k_coverage.hip, k_pileup.hip, k_abundance.hip): each handle's struct derives from Accum (accum.h)
+const Accum *as_accum(const mnc_coverage *cv);
+const Accum *as_accum(const mnc_pileup *pu);
+const Accum *as_accum(const mnc_abundance *ab);
 int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream_t st);
-// pileup accumulator (k_pileup.hip)
-const mnc_index *pileup_index(const mnc_pileup *pu);
-int pileup_device_of(const mnc_pileup *pu);
 int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st);
-// abundance accumulator (k_abundance.hip)
-const mnc_index *abundance_index(const mnc_abundance *ab);
-int abundance_device_of(const mnc_abundance *ab);
 int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st);
-
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-	return e_ == hipErrorOutOfMemory ? MNC_ERR_NOMEM : MNC_ERR_HIP; } } while (0)
 
 // ---------------------------------------------------------------- run offsets of the partition
 // The sketch writes one histogram row per tile ([tile][bucket]); the query records are laid out
@@ -205,7 +197,7 @@ static SharedWs *shared_ws(int device, int add_ref)
 }
 
 // ================================================================ index residency
-int check_device(int device)                                // (k_coverage.hip, k_pileup.hip and k_abundance.hip use it as well)
+int check_device(int device)                                // (accum.h: the accumulators use it as well)
 {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible"); return MNC_ERR_NODEVICE; }
@@ -1735,25 +1727,44 @@ extern "C" int mnc_engine_export_ms(mnc_engine *e, double *ms)
 // ---------------------------------------------------------------- coverage of the last batch
 // Adds the batch as it stands in HBM (regions, region CIGARs, decisions) to an accumulator (k_coverage.hip): one kernel on
 // the engine's stream, no read-back.  Every check comes before the launch, so an error leaves the accumulator as it was.
-extern "C" int mnc_engine_add_coverage(mnc_engine *e, mnc_coverage *cov, int what)
+constexpr int COV_SELECTORS = MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED;
+
+// the selector of `what`; a pileup takes nothing beside it
+static int add_selector(int what, bool pileup, int *sel)
 {
-	if (!e || !cov) return MNC_ERR_ARG;
-	const int sel = what & (MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED);
-	if (what & ~(MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED | MNC_COV_SPAN)) { set_error("unknown bits in `what` (0x%x)", what); return MNC_ERR_ARG; }
-	if (sel == 0 || (sel & (sel - 1))) { set_error("exactly one of MNC_COV_GATED / PRIMARY / ALL / ASSIGNED is required"); return MNC_ERR_ARG; }
-	if (coverage_index(cov) != e->idx || coverage_device_of(cov) != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
+	if (pileup && (what & ~COV_SELECTORS)) { set_error("`what` (0x%x) holds more than a selector (MNC_COV_SPAN has no meaning for a pileup)", what); return MNC_ERR_ARG; }
+	if (what & ~(COV_SELECTORS | MNC_COV_SPAN)) { set_error("unknown bits in `what` (0x%x)", what); return MNC_ERR_ARG; }
+	*sel = what & COV_SELECTORS;
+	if (*sel == 0 || (*sel & (*sel - 1))) { set_error("exactly one of MNC_COV_GATED / PRIMARY / ALL / ASSIGNED is required"); return MNC_ERR_ARG; }
+	return MNC_OK;
+}
+
+// What every add checks, beside its selector, before it touches anything.  noun: what the call adds, for the wide-pass
+// refusal.  need_dp: the message when the batch's contract is not MNC_CONTRACT_DP; nullptr where any contract serves.
+static int add_precheck(const mnc_engine *e, const Accum *a, const char *noun, const char *need_dp)
+{
+	if (!e || !a) return MNC_ERR_ARG;
+	if (a->idx != e->idx || a->device != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
 	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
 	if (e->have_merged) {
 		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
-		          "alone -- classify the two groups in separate calls to add their coverage");
+		          "alone -- classify the two groups in separate calls to add their %s", noun);
 		return MNC_ERR_UNSUPPORTED;
 	}
-	const Batch &B = e->B;
+	if (need_dp && (e->B.n_reads ? e->B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("%s", need_dp); return MNC_ERR_ARG; }
+	return MNC_OK;
+}
+
+extern "C" int mnc_engine_add_coverage(mnc_engine *e, mnc_coverage *cov, int what)
+{
+	if (!e || !cov) return MNC_ERR_ARG;
+	int sel = 0;
 	const bool span = (what & MNC_COV_SPAN) != 0;
-	if (!span && (B.n_reads ? B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("MNC_COV_SPAN is required under MNC_CONTRACT_CHAIN (no CIGAR)"); return MNC_ERR_ARG; }
-	if (B.n_reads == 0) return MNC_OK;
+	if (int rc = add_selector(what, false, &sel)) return rc;
+	if (int rc = add_precheck(e, as_accum(cov), "coverage", span ? nullptr : "MNC_COV_SPAN is required under MNC_CONTRACT_CHAIN (no CIGAR)")) return rc;
+	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
-	return coverage_add(cov, B, sel, span, e->stream);
+	return coverage_add(cov, e->B, sel, span, e->stream);
 }
 
 // ---------------------------------------------------------------- pileup of the last batch
@@ -1761,40 +1772,22 @@ extern "C" int mnc_engine_add_coverage(mnc_engine *e, mnc_coverage *cov, int wha
 extern "C" int mnc_engine_add_pileup(mnc_engine *e, mnc_pileup *pu, int what)
 {
 	if (!e || !pu) return MNC_ERR_ARG;
-	const int sel = what & (MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED);
-	if (what & ~(MNC_COV_GATED | MNC_COV_PRIMARY | MNC_COV_ALL | MNC_COV_ASSIGNED)) { set_error("`what` (0x%x) holds more than a selector (MNC_COV_SPAN has no meaning for a pileup)", what); return MNC_ERR_ARG; }
-	if (sel == 0 || (sel & (sel - 1))) { set_error("exactly one of MNC_COV_GATED / PRIMARY / ALL / ASSIGNED is required"); return MNC_ERR_ARG; }
-	if (pileup_index(pu) != e->idx || pileup_device_of(pu) != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
-	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
-	if (e->have_merged) {
-		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
-		          "alone -- classify the two groups in separate calls to add their pileup");
-		return MNC_ERR_UNSUPPORTED;
-	}
-	const Batch &B = e->B;
-	if ((B.n_reads ? B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("a pileup needs the CIGARs of MNC_CONTRACT_DP"); return MNC_ERR_ARG; }
-	if (B.n_reads == 0) return MNC_OK;
+	int sel = 0;
+	if (int rc = add_selector(what, true, &sel)) return rc;
+	if (int rc = add_precheck(e, as_accum(pu), "pileup", "a pileup needs the CIGARs of MNC_CONTRACT_DP")) return rc;
+	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
-	return pileup_add(pu, B, sel, e->stream);
+	return pileup_add(pu, e->B, sel, e->stream);
 }
 
 // ---------------------------------------------------------------- abundance candidates of the last batch
 // The same for the EM's candidate lists (k_abundance.hip): every record with a CIGAR, as MNC_COV_ALL walks them.
 extern "C" int mnc_engine_add_abundance(mnc_engine *e, mnc_abundance *ab)
 {
-	if (!e || !ab) return MNC_ERR_ARG;
-	if (abundance_index(ab) != e->idx || abundance_device_of(ab) != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
-	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
-	if (e->have_merged) {
-		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
-		          "alone -- classify the two groups in separate calls to add their abundance candidates");
-		return MNC_ERR_UNSUPPORTED;
-	}
-	const Batch &B = e->B;
-	if ((B.n_reads ? B.contract : e->contract) != MNC_CONTRACT_DP) { set_error("abundance candidates need the dp_max of MNC_CONTRACT_DP"); return MNC_ERR_ARG; }
-	if (B.n_reads == 0) return MNC_OK;
+	if (int rc = add_precheck(e, as_accum(ab), "abundance candidates", "abundance candidates need the dp_max of MNC_CONTRACT_DP")) return rc;
+	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
-	return abundance_add(ab, B, e->stream);
+	return abundance_add(ab, e->B, e->stream);
 }
 
 // ---------------------------------------------------------------- counters / dumps

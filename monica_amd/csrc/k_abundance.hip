@@ -32,7 +32,6 @@
 //                    between blocks.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <mutex>
 #include <new>
 #include <vector>
 #include "device.h"
@@ -41,12 +40,9 @@
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
 #include "cov_common.h"
 #pragma clang diagnostic pop
+#include "accum.h"
 
 using namespace mnc;
-
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-	return e_ == hipErrorOutOfMemory ? MNC_ERR_NOMEM : MNC_ERR_HIP; } } while (0)
 
 constexpr int AB_LDS_G = 2048;                 // genomes whose theta and private acc fit a workgroup's LDS (16 bytes each)
 constexpr int AB_LAUNCH_BLOCK = 256;           // iterations queued before the "done" word is looked at
@@ -59,9 +55,8 @@ constexpr int ABC_PACK = 0, ABC_READS = 1, ABC_DROPPED = 2, ABC_N = 4;
 // solver state (uint64 words of `state`)
 constexpr int ABS_DONE = 0, ABS_ITERS = 1, ABS_LAST = 2, ABS_N = 4;
 
-struct mnc_abundance {
-	mnc_index *idx = nullptr;
-	int device = 0, n_contigs = 0, G = 0;
+struct mnc_abundance : Accum {                 // (ev_own: the last reset or add_lists)
+	int n_contigs = 0, G = 0;
 	int64_t cap_cands = 0, cap_rows = 0;
 	int32_t max_delta = 0, scale_q = 0;
 	int64_t *unique = nullptr;                 // [G]
@@ -71,16 +66,9 @@ struct mnc_abundance {
 	double *theta = nullptr;                   // [G]
 	unsigned long long *acc = nullptr;         // [2][G]
 	unsigned long long *state = nullptr;       // [ABS_N]
-	int64_t bytes = 0;
-	// adds run on the engines' streams, from their threads; everything else on this one (k_pileup.hip: the same events)
-	std::mutex mu;
-	hipStream_t st = nullptr;
-	hipEvent_t ev_add = nullptr, ev_own = nullptr;
 };
 
 namespace mnc {
-
-int check_device(int device);                  // engine.hip
 
 // ---------------------------------------------------------------- collect
 __device__ __forceinline__ unsigned long long ab_wave_min(unsigned long long x)
@@ -285,21 +273,16 @@ __global__ __launch_bounds__(256) void mnc_ab_append(int G, const int64_t *uniq_
 }
 
 // ---------------------------------------------------------------- the engine's side (mnc_engine_add_abundance, engine.hip)
-const mnc_index *abundance_index(const mnc_abundance *ab) { return ab->idx; }
-int abundance_device_of(const mnc_abundance *ab) { return ab->device; }
+const Accum *as_accum(const mnc_abundance *ab) { return ab; }
 
 // the batch B, as it stands in HBM, on the engine's stream `st`; nothing waits on the host
 int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st)
 {
 	if (B.n_reads == 0 || ab->G == 0) return MNC_OK;
-	std::lock_guard<std::mutex> lk(ab->mu);
-	HIP_TRY(hipStreamWaitEvent(st, ab->ev_own, 0));            // behind the last reset / add_lists
-	hipLaunchKernelGGL(mnc_ab_collect, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, ab->n_contigs, ab->G, (int)ab->max_delta, ab->cap_cands, ab->cap_rows,
-	                   ab->unique, ab->offsets, ab->genome, ab->delta, ab->ctr);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(ab->ev_add, st));
-	HIP_TRY(hipStreamWaitEvent(ab->st, ab->ev_add, 0));        // reset, add_lists and the read-outs come after it
-	return MNC_OK;
+	return ab->add(st, [&] {
+		hipLaunchKernelGGL(mnc_ab_collect, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, ab->n_contigs, ab->G, (int)ab->max_delta, ab->cap_cands, ab->cap_rows,
+		                   ab->unique, ab->offsets, ab->genome, ab->delta, ab->ctr);
+	});
 }
 
 } // namespace mnc
@@ -317,13 +300,7 @@ static int ab_counters(mnc_abundance *ab, unsigned long long *c)
 extern "C" void mnc_abundance_free(mnc_abundance *ab)
 {
 	if (!ab) return;
-	(void)hipSetDevice(ab->device);
-	if (ab->st) (void)hipStreamSynchronize(ab->st);
-	for (void *p : { (void*)ab->unique, (void*)ab->offsets, (void*)ab->genome, (void*)ab->delta, (void*)ab->ctr, (void*)ab->theta, (void*)ab->acc, (void*)ab->state })
-		if (p) (void)hipFree(p);
-	if (ab->ev_add) (void)hipEventDestroy(ab->ev_add);
-	if (ab->ev_own) (void)hipEventDestroy(ab->ev_own);
-	if (ab->st) (void)hipStreamDestroy(ab->st);
+	ab->release();
 	delete ab;
 }
 
@@ -339,33 +316,24 @@ extern "C" int mnc_abundance_create(mnc_index *idx, int device, int64_t cap_cand
 	if (int rc = check_device(device)) return rc;
 	mnc_abundance *ab = new (std::nothrow) mnc_abundance;
 	if (!ab) return MNC_ERR_NOMEM;
-	ab->idx = idx, ab->device = device, ab->n_contigs = (int)idx->contig_len.size(), ab->G = (int)idx->genome_name.size();
+	ab->n_contigs = (int)idx->contig_len.size(), ab->G = (int)idx->genome_name.size();
 	ab->cap_cands = cap_cands, ab->cap_rows = cap_cands / 2, ab->max_delta = max_delta, ab->scale_q = scale_q;
 	const size_t G = (size_t)ab->G;
-	hipError_t he = hipSetDevice(device);
-	auto alloc = [&](void **p, size_t bytes) {
-		if (he != hipSuccess) return;
-		bytes = bytes ? bytes : 8;
-		he = hipMalloc(p, bytes);
-		if (he == hipSuccess) ab->bytes += (int64_t)bytes; else *p = nullptr;
-	};
-	alloc((void**)&ab->unique, G * 8);
-	alloc((void**)&ab->offsets, ((size_t)ab->cap_rows + 1) * 8);
-	alloc((void**)&ab->genome, (size_t)cap_cands * 4);
-	alloc((void**)&ab->delta, (size_t)cap_cands * 4);
-	alloc((void**)&ab->ctr, ABC_N * 8);
-	alloc((void**)&ab->theta, G * 8);
-	alloc((void**)&ab->acc, G * 16);
-	alloc((void**)&ab->state, ABS_N * 8);
-	const bool nomem = he == hipErrorOutOfMemory;
-	if (he == hipSuccess) he = hipStreamCreateWithFlags(&ab->st, hipStreamNonBlocking);
-	if (he == hipSuccess) he = hipEventCreateWithFlags(&ab->ev_add, hipEventDisableTiming);
-	if (he == hipSuccess) he = hipEventCreateWithFlags(&ab->ev_own, hipEventDisableTiming);
+	hipError_t he = ab->begin(idx, device);
+	ab->alloc(he, (void**)&ab->unique, G * 8);
+	ab->alloc(he, (void**)&ab->offsets, ((size_t)ab->cap_rows + 1) * 8);
+	ab->alloc(he, (void**)&ab->genome, (size_t)cap_cands * 4);
+	ab->alloc(he, (void**)&ab->delta, (size_t)cap_cands * 4);
+	ab->alloc(he, (void**)&ab->ctr, ABC_N * 8);
+	ab->alloc(he, (void**)&ab->theta, G * 8);
+	ab->alloc(he, (void**)&ab->acc, G * 16);
+	ab->alloc(he, (void**)&ab->state, ABS_N * 8);
+	ab->streams(he);
 	if (he != hipSuccess) {
 		set_error("abundance accumulator of %lld candidate slots (12 bytes each): %s", (long long)cap_cands, hipGetErrorString(he));
-		(void)hipGetLastError();
+		const int rc = Accum::failed(he);
 		mnc_abundance_free(ab);
-		return nomem ? MNC_ERR_NOMEM : MNC_ERR_HIP;
+		return rc;
 	}
 	if (int rc = mnc_abundance_reset(ab)) { mnc_abundance_free(ab); return rc; }
 	*out = ab;
@@ -380,16 +348,11 @@ extern "C" int mnc_abundance_reset(mnc_abundance *ab)
 	HIP_TRY(hipMemsetAsync(ab->unique, 0, ab->G ? (size_t)ab->G * 8 : 8, ab->st));
 	HIP_TRY(hipMemsetAsync(ab->offsets, 0, 8, ab->st));        // offsets[0]: the CSR of no rows
 	HIP_TRY(hipMemsetAsync(ab->ctr, 0, ABC_N * 8, ab->st));
-	HIP_TRY(hipEventRecord(ab->ev_own, ab->st));
+	HIP_TRY(ab->own_done());
 	return MNC_OK;
 }
 
-extern "C" int mnc_abundance_device_bytes(const mnc_abundance *ab, int64_t *bytes)
-{
-	if (!ab || !bytes) return MNC_ERR_ARG;
-	*bytes = ab->bytes;
-	return MNC_OK;
-}
+extern "C" int mnc_abundance_device_bytes(const mnc_abundance *ab, int64_t *bytes) { return accum_device_bytes(ab, bytes); }
 
 extern "C" int mnc_abundance_device(mnc_abundance *ab, const int64_t **d_unique, const int64_t **d_offsets, const int32_t **d_genome, const int32_t **d_delta)
 {
@@ -525,7 +488,7 @@ extern "C" int mnc_abundance_add_lists(mnc_abundance *ab, int64_t n_reads, const
 		                   pack, (unsigned long long)n_reads);
 		he = hipGetLastError();
 	}
-	if (he == hipSuccess) he = hipEventRecord(ab->ev_own, ab->st);   // an engine's add comes behind it
+	if (he == hipSuccess) he = ab->own_done();                   // an engine's add comes behind it
 	const hipError_t hs = hipStreamSynchronize(ab->st);          // the host arrays above are read until here
 	if (he == hipSuccess) he = hs;
 	(void)hipFree(d_inc);

@@ -12,16 +12,11 @@
 //   contig's last word, and the track stays at exactly 4 bytes per base in the layout a caller's collective expects.
 //   Consequence: the words of a contig do not sum to zero, and the summary must not let one contig's sum run into the next.
 //
-//   mnc_cov_add_runs   one wave per READ (not per record: a read's live region slots are found as k_export.hip finds them,
-//                      reg_slot(r) .. + n_reg[r], which needs no scan over the batch, no record list and no host wait; a
-//                      read has a handful of records).  Every lane walks the read's records -- the selection is decided
-//                      on the way, for MNC_COV_ASSIGNED by best_hit's int64 cross-products over the gated records -- and
-//                      the wave walks a selected record's CIGAR 64 operations at a time: reference offsets by a prefix
-//                      sum of the reference-consuming lengths, one ballot each of the M and the D operations.  A covered
-//                      run is a maximal stretch of M columns without a D (insertions consume no reference and do not break
-//                      it): the M lane whose nearest M / D neighbour below is a D (or none, with no run carried in) opens
-//                      it, the D lane whose nearest neighbour below is an M closes it at its own start.  Whether a run is
-//                      open across a chunk border is one carried scalar; lane 0 closes the last run after the loop.
+//   mnc_cov_add_runs   one wave per READ (not per record: a read has a handful of records, cov_for_records).  Every lane
+//                      walks the read's records -- the selection is decided on the way, for MNC_COV_ASSIGNED by best_hit's
+//                      int64 cross-products over the gated records -- and the wave walks a selected record's CIGAR 64
+//                      operations at a time: reference offsets by a prefix sum of the reference-consuming lengths, the
+//                      covered runs by cov_run_step (cov_common.h).
 //   mnc_cov_add_span   one lane per read: +1 at rs, -1 at re of every selected record (MNC_COV_SPAN)
 //   mnc_cov_scan       the summary.  Restarting the sum at every contig needs no segmented operator: with G the plain
 //                      running sum of the whole track, depth(c, p) = G(off[c] + p) - G(off[c] - 1), so scan.h's tile sums
@@ -35,17 +30,13 @@
 #include <vector>
 #include "device.h"
 #include "scan.h"
-#include "cov_common.h"                        // the selectors, cov_put, mnc_cov_contig_base: shared with k_pileup.hip
+#include "cov_scan.h"                          // with cov_common.h: the selectors, the record walk, the runs, the tile sums: shared with k_pileup.hip
+#include "accum.h"
 
 using namespace mnc;
 
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-	return e_ == hipErrorOutOfMemory ? MNC_ERR_NOMEM : MNC_ERR_HIP; } } while (0)
-
-struct mnc_coverage {
-	mnc_index *idx = nullptr;
-	int device = 0, bin_bases = 0, n_contigs = 0;
+struct mnc_coverage : Accum {
+	int bin_bases = 0, n_contigs = 0;
 	int64_t n_words = 0;                       // = the index's total_len
 	std::vector<int64_t> off;                  // n_contigs + 1
 	int32_t *track = nullptr;                  // [n_words] depth differences
@@ -55,36 +46,22 @@ struct mnc_coverage {
 	long long *cbase = nullptr;                // [n_contigs] running sum of the track before the contig (scratch)
 	unsigned long long *c_cov = nullptr, *c_sum = nullptr;   // [n_contigs] each: the summary's results
 	int32_t *c_max = nullptr;
-	int64_t bytes = 0;
-	// adds run on the engines' streams; reset and the summaries on this one.  ev_add: the last add (this stream waits
-	// for it); ev_own: the last reset / summary (an add waits for it)
-	hipStream_t st = nullptr;
-	hipEvent_t ev_add = nullptr, ev_own = nullptr;
 };
 
 namespace mnc {
-
-int check_device(int device);                  // engine.hip
 
 __global__ __launch_bounds__(256) void mnc_cov_add_runs(Batch B, int sel, const int64_t *off, int n_contigs, int32_t *track, unsigned long long *n_aln)
 {
 	const int lane = lane_id();
 	const uint32_t rd = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
 	if (rd >= B.n_reads) return;                              // (whole waves; the kernel has no workgroup barrier)
-	const int n = B.n_reg[rd];
-	if (n <= 0) return;
-	const int64_t slot0 = reg_slot(B, rd);
-	const int pick = sel == MNC_COV_ASSIGNED ? cov_pick(B, rd, slot0, n) : -1;
-	if (sel == MNC_COV_ASSIGNED && pick < 0) return;
-	for (int i = pick < 0 ? 0 : pick; i < (pick < 0 ? n : pick + 1); ++i) {
-		const mnc_reg_t r = B.regs[slot0 + i];
-		if (!cov_selected(r, sel, B.min_mapq) || r.rid < 0 || r.rid >= n_contigs) continue;
+	cov_for_records(B, rd, sel, n_contigs, [&](const mnc_reg_t &r, int64_t slot) {
 		const int64_t len = off[r.rid + 1] - off[r.rid];
 		int32_t *w = track + off[r.rid];
 		if (lane == 0) (void)__hip_atomic_fetch_add(n_aln + r.rid, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		const int n_c = r.n_cigar;
-		if (n_c <= 0) continue;
-		const uint32_t *src = B.cig_reg + B.regdp[slot0 + i].cig_off;
+		if (n_c <= 0) return;
+		const uint32_t *src = B.cig_reg + B.regdp[slot].cig_off;
 		int64_t toff = r.rs;                                   // reference position before the chunk at hand
 		bool open = false;                                     // a run is open: the last M / D operation so far was an M
 		for (int k0 = 0; k0 < n_c; k0 += 64) {
@@ -94,38 +71,23 @@ __global__ __launch_bounds__(256) void mnc_cov_add_runs(Batch B, int sel, const 
 			const int l = k < n_c && op <= 2 ? (int)(wd >> 4) : 0;
 			const int dt = op != 1 ? l : 0;
 			const int it = cov_incl_add(dt);
-			const int64_t t0 = toff + it - dt;
-			const bool is_M = l > 0 && op == 0, is_D = l > 0 && op == 2;
-			const unsigned long long m_M = __ballot(is_M), m_D = __ballot(is_D);
-			const unsigned long long below = (m_M | m_D) & ((1ull << lane) - 1ull);
-			const bool prev_M = below ? (m_M >> (63 - __clzll((long long)below)) & 1ull) != 0 : open;
-			if (is_M && !prev_M) cov_put(w, len, t0, 1);
-			if (is_D && prev_M) cov_put(w, len, t0, -1);
-			const unsigned long long any = m_M | m_D;
-			if (any) open = (m_M >> (63 - __clzll((long long)any)) & 1ull) != 0;
+			cov_run_step(w, len, l > 0 && op == 0, l > 0 && op == 2, toff + it - dt, open);
 			toff += __shfl(it, 63);
 		}
-		if (open && lane == 0) cov_put(w, len, toff, -1);
-	}
+		cov_run_close(w, len, toff, open);
+	});
 }
 
 __global__ __launch_bounds__(256) void mnc_cov_add_span(Batch B, int sel, const int64_t *off, int n_contigs, int32_t *track, unsigned long long *n_aln)
 {
 	const uint32_t rd = blockIdx.x * blockDim.x + threadIdx.x;
 	if (rd >= B.n_reads) return;
-	const int n = B.n_reg[rd];
-	if (n <= 0) return;
-	const int64_t slot0 = reg_slot(B, rd);
-	const int pick = sel == MNC_COV_ASSIGNED ? cov_pick(B, rd, slot0, n) : -1;
-	if (sel == MNC_COV_ASSIGNED && pick < 0) return;
-	for (int i = pick < 0 ? 0 : pick; i < (pick < 0 ? n : pick + 1); ++i) {
-		const mnc_reg_t &r = B.regs[slot0 + i];
-		if (!cov_selected(r, sel, B.min_mapq) || r.rid < 0 || r.rid >= n_contigs) continue;
+	cov_for_records(B, rd, sel, n_contigs, [&](const mnc_reg_t &r, int64_t) {
 		const int64_t len = off[r.rid + 1] - off[r.rid];
 		int32_t *w = track + off[r.rid];
 		(void)__hip_atomic_fetch_add(n_aln + r.rid, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		if (r.re > r.rs) cov_put(w, len, r.rs, 1), cov_put(w, len, r.re, -1);
-	}
+	});
 }
 
 struct CovAcc {
@@ -251,30 +213,22 @@ __global__ __launch_bounds__(SC_THREADS) void mnc_cov_scan(const int32_t *track,
 template <int MODE>
 static void cov_launch_scan(mnc_coverage *cv, const int32_t *track, int64_t n, int32_t *b_cov, unsigned long long *b_sum, int64_t start, int32_t *depth)
 {
-	const int64_t nb = (n + SC_TILE - 1) / SC_TILE;
-	hipStream_t st = cv->st;
-	hipLaunchKernelGGL(mnc_scan_reduce<ScanInPlain<int32_t>>, dim3((unsigned)nb), dim3(SC_THREADS), 0, st, ScanInPlain<int32_t>{track}, n, cv->tile_sums);
-	hipLaunchKernelGGL(mnc_scan_sums, dim3(1), dim3(64), 0, st, cv->tile_sums, nb);
-	if (MODE == 0) hipLaunchKernelGGL(mnc_cov_contig_base, dim3((unsigned)((cv->n_contigs + 3) / 4)), dim3(256), 0, st, track, cv->d_off, cv->n_contigs, cv->tile_sums, cv->cbase);
-	hipLaunchKernelGGL(mnc_cov_scan<MODE>, dim3((unsigned)nb), dim3(SC_THREADS), 0, st, track, n, cv->tile_sums, cv->d_off, cv->n_contigs, cv->cbase,
+	cov_tile_sums(track, n, cv->tile_sums, cv->d_off, cv->n_contigs, MODE == 0 ? cv->cbase : nullptr, cv->st);
+	hipLaunchKernelGGL(mnc_cov_scan<MODE>, dim3((unsigned)((n + SC_TILE - 1) / SC_TILE)), dim3(SC_THREADS), 0, cv->st, track, n, cv->tile_sums, cv->d_off, cv->n_contigs, cv->cbase,
 	                   MODE == 0 ? cv->c_cov : nullptr, MODE == 0 ? cv->c_sum : b_sum, MODE == 0 ? cv->c_max : nullptr, cv->bin_bases, b_cov, start, depth);
 }
 
 // ---------------------------------------------------------------- the engine's side (mnc_engine_add_coverage, engine.hip)
-const mnc_index *coverage_index(const mnc_coverage *cv) { return cv->idx; }
-int coverage_device_of(const mnc_coverage *cv) { return cv->device; }
+const Accum *as_accum(const mnc_coverage *cv) { return cv; }
 
 // the batch B, as it stands in HBM, on the engine's stream `st`; nothing waits on the host
 int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream_t st)
 {
 	if (B.n_reads == 0 || cv->n_words == 0) return MNC_OK;
-	HIP_TRY(hipStreamWaitEvent(st, cv->ev_own, 0));            // behind the last reset
-	if (span) hipLaunchKernelGGL(mnc_cov_add_span, dim3((B.n_reads + 255) / 256), dim3(256), 0, st, B, sel, cv->d_off, cv->n_contigs, cv->track, cv->n_aln);
-	else hipLaunchKernelGGL(mnc_cov_add_runs, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, cv->d_off, cv->n_contigs, cv->track, cv->n_aln);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(cv->ev_add, st));
-	HIP_TRY(hipStreamWaitEvent(cv->st, cv->ev_add, 0));        // reset and the summaries come after it
-	return MNC_OK;
+	return cv->add(st, [&] {
+		if (span) hipLaunchKernelGGL(mnc_cov_add_span, dim3((B.n_reads + 255) / 256), dim3(256), 0, st, B, sel, cv->d_off, cv->n_contigs, cv->track, cv->n_aln);
+		else hipLaunchKernelGGL(mnc_cov_add_runs, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, cv->d_off, cv->n_contigs, cv->track, cv->n_aln);
+	});
 }
 
 } // namespace mnc
@@ -283,13 +237,7 @@ int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream
 extern "C" void mnc_coverage_free(mnc_coverage *cv)
 {
 	if (!cv) return;
-	(void)hipSetDevice(cv->device);
-	if (cv->st) (void)hipStreamSynchronize(cv->st);
-	for (void *p : { (void*)cv->track, (void*)cv->n_aln, (void*)cv->d_off, (void*)cv->tile_sums, (void*)cv->cbase, (void*)cv->c_cov, (void*)cv->c_sum, (void*)cv->c_max })
-		if (p) (void)hipFree(p);
-	if (cv->ev_add) (void)hipEventDestroy(cv->ev_add);
-	if (cv->ev_own) (void)hipEventDestroy(cv->ev_own);
-	if (cv->st) (void)hipStreamDestroy(cv->st);
+	cv->release();
 	delete cv;
 }
 
@@ -301,38 +249,29 @@ extern "C" int mnc_coverage_create(mnc_index *idx, int device, int bin_bases, mn
 	if (int rc = check_device(device)) return rc;
 	mnc_coverage *cv = new (std::nothrow) mnc_coverage;
 	if (!cv) return MNC_ERR_NOMEM;
-	cv->idx = idx, cv->device = device, cv->bin_bases = bin_bases, cv->n_contigs = (int)idx->contig_len.size();
+	cv->bin_bases = bin_bases, cv->n_contigs = (int)idx->contig_len.size();
 	try {
 		cv->off.assign((size_t)cv->n_contigs + 1, 0);
 	} catch (const std::bad_alloc &) { delete cv; return MNC_ERR_NOMEM; }
 	for (int c = 0; c < cv->n_contigs; ++c) cv->off[c + 1] = cv->off[c] + idx->contig_len[c];
 	cv->n_words = cv->off[cv->n_contigs];
 	const size_t nc = (size_t)cv->n_contigs, nw = (size_t)cv->n_words;
-	hipError_t he = hipSetDevice(device);
-	auto alloc = [&](void **p, size_t bytes) {
-		if (he != hipSuccess) return;
-		bytes = bytes ? bytes : 8;
-		he = hipMalloc(p, bytes);
-		if (he == hipSuccess) cv->bytes += (int64_t)bytes; else *p = nullptr;
-	};
-	alloc((void**)&cv->track, nw * 4);
-	alloc((void**)&cv->n_aln, nc * 8);
-	alloc((void**)&cv->d_off, (nc + 1) * 8);
-	alloc((void**)&cv->tile_sums, (nw / SC_TILE + 2) * 8);
-	alloc((void**)&cv->cbase, nc * 8);
-	alloc((void**)&cv->c_cov, nc * 8);
-	alloc((void**)&cv->c_sum, nc * 8);
-	alloc((void**)&cv->c_max, nc * 4);
-	const bool nomem = he == hipErrorOutOfMemory;
-	if (he == hipSuccess) he = hipStreamCreateWithFlags(&cv->st, hipStreamNonBlocking);
-	if (he == hipSuccess) he = hipEventCreateWithFlags(&cv->ev_add, hipEventDisableTiming);
-	if (he == hipSuccess) he = hipEventCreateWithFlags(&cv->ev_own, hipEventDisableTiming);
+	hipError_t he = cv->begin(idx, device);
+	cv->alloc(he, (void**)&cv->track, nw * 4);
+	cv->alloc(he, (void**)&cv->n_aln, nc * 8);
+	cv->alloc(he, (void**)&cv->d_off, (nc + 1) * 8);
+	cv->alloc(he, (void**)&cv->tile_sums, (nw / SC_TILE + 2) * 8);
+	cv->alloc(he, (void**)&cv->cbase, nc * 8);
+	cv->alloc(he, (void**)&cv->c_cov, nc * 8);
+	cv->alloc(he, (void**)&cv->c_sum, nc * 8);
+	cv->alloc(he, (void**)&cv->c_max, nc * 4);
+	cv->streams(he);
 	if (he == hipSuccess) he = hipMemcpy(cv->d_off, cv->off.data(), (nc + 1) * 8, hipMemcpyHostToDevice);
 	if (he != hipSuccess) {
 		set_error("coverage accumulator of %lld bases: %s", (long long)cv->n_words, hipGetErrorString(he));
-		(void)hipGetLastError();
+		const int rc = Accum::failed(he);
 		mnc_coverage_free(cv);
-		return nomem ? MNC_ERR_NOMEM : MNC_ERR_HIP;
+		return rc;
 	}
 	if (int rc = mnc_coverage_reset(cv)) { mnc_coverage_free(cv); return rc; }
 	*out = cv;
@@ -343,18 +282,14 @@ extern "C" int mnc_coverage_reset(mnc_coverage *cv)
 {
 	if (!cv) return MNC_ERR_ARG;
 	HIP_TRY(hipSetDevice(cv->device));
+	std::lock_guard<std::mutex> lk(cv->mu);
 	if (cv->n_words) HIP_TRY(hipMemsetAsync(cv->track, 0, (size_t)cv->n_words * 4, cv->st));
 	if (cv->n_contigs) HIP_TRY(hipMemsetAsync(cv->n_aln, 0, (size_t)cv->n_contigs * 8, cv->st));
-	HIP_TRY(hipEventRecord(cv->ev_own, cv->st));
+	HIP_TRY(cv->own_done());
 	return MNC_OK;
 }
 
-extern "C" int mnc_coverage_device_bytes(const mnc_coverage *cv, int64_t *bytes)
-{
-	if (!cv || !bytes) return MNC_ERR_ARG;
-	*bytes = cv->bytes;
-	return MNC_OK;
-}
+extern "C" int mnc_coverage_device_bytes(const mnc_coverage *cv, int64_t *bytes) { return accum_device_bytes(cv, bytes); }
 
 extern "C" int mnc_coverage_summary(mnc_coverage *cv, int64_t *covered, int64_t *depth_sum, int32_t *max_depth, int64_t *n_aln)
 {
@@ -386,48 +321,24 @@ extern "C" int mnc_coverage_fetch_bins(mnc_coverage *cv, int rid, int32_t *bin_c
 	if (cap < nb) { set_error("contig %d has %lld bins of %d bases", rid, (long long)nb, cv->bin_bases); return MNC_ERR_RANGE; }
 	if (nb == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(cv->device));
-	hipStream_t st = cv->st;
 	char *tmp = nullptr;                                        // [nb] depth sums, then [nb] covered bases
 	HIP_TRY(hipMalloc((void**)&tmp, (size_t)nb * 12));
-	int rc = MNC_OK;
-	hipError_t he = hipMemsetAsync(tmp, 0, (size_t)nb * 12, st);
-	if (he == hipSuccess) {
-		cov_launch_scan<1>(cv, cv->track + cv->off[rid], len, (int32_t*)(tmp + (size_t)nb * 8), (unsigned long long*)tmp, 0, nullptr);
-		he = hipGetLastError();
-	}
-	if (he == hipSuccess && bin_depth_sum) he = hipMemcpyAsync(bin_depth_sum, tmp, (size_t)nb * 8, hipMemcpyDeviceToHost, st);
-	if (he == hipSuccess && bin_covered) he = hipMemcpyAsync(bin_covered, tmp + (size_t)nb * 8, (size_t)nb * 4, hipMemcpyDeviceToHost, st);
-	const hipError_t hs = hipStreamSynchronize(st);
-	if (he == hipSuccess) he = hs;
-	if (he != hipSuccess) { set_error("bins of contig %d: %s", rid, hipGetErrorString(he)); rc = MNC_ERR_HIP; }
-	(void)hipFree(tmp);
-	return rc;
+	const hipError_t he = hipMemsetAsync(tmp, 0, (size_t)nb * 12, cv->st);
+	if (he == hipSuccess) cov_launch_scan<1>(cv, cv->track + cv->off[rid], len, (int32_t*)(tmp + (size_t)nb * 8), (unsigned long long*)tmp, 0, nullptr);
+	return cv->finish(he, tmp, {bin_depth_sum, tmp, (size_t)nb * 8}, {bin_covered, tmp + (size_t)nb * 8, (size_t)nb * 4}, "bins of contig %d", rid);
 }
 
 extern "C" int mnc_coverage_fetch_depth(mnc_coverage *cv, int rid, int64_t start, int64_t end, int32_t *depth)
 {
 	if (!cv) return MNC_ERR_ARG;
-	if (rid < 0 || rid >= cv->n_contigs) { set_error("contig %d out of range", rid); return MNC_ERR_ARG; }
-	const int64_t len = cv->off[rid + 1] - cv->off[rid];
-	if (start < 0 || end < start || end > len) {
-		set_error("interval [%lld, %lld) outside contig %d of %lld bases", (long long)start, (long long)end, rid, (long long)len);
-		return MNC_ERR_ARG;
-	}
+	if (int rc = accum_interval(cv->off, rid, start, end)) return rc;
 	if (end == start) return MNC_OK;
 	if (!depth) return MNC_ERR_ARG;
 	HIP_TRY(hipSetDevice(cv->device));
-	hipStream_t st = cv->st;
 	int32_t *tmp = nullptr;
 	HIP_TRY(hipMalloc((void**)&tmp, (size_t)(end - start) * 4));
-	int rc = MNC_OK;
 	cov_launch_scan<2>(cv, cv->track + cv->off[rid], end, nullptr, nullptr, start, tmp);   // the contig's words up to `end`: the sum starts at the contig
-	hipError_t he = hipGetLastError();
-	if (he == hipSuccess) he = hipMemcpyAsync(depth, tmp, (size_t)(end - start) * 4, hipMemcpyDeviceToHost, st);
-	const hipError_t hs = hipStreamSynchronize(st);
-	if (he == hipSuccess) he = hs;
-	if (he != hipSuccess) { set_error("depth of contig %d: %s", rid, hipGetErrorString(he)); rc = MNC_ERR_HIP; }
-	(void)hipFree(tmp);
-	return rc;
+	return cv->finish(hipSuccess, tmp, {depth, tmp, (size_t)(end - start) * 4}, {}, "depth of contig %d", rid);
 }
 
 extern "C" int mnc_coverage_device(mnc_coverage *cv, const int32_t **d_track, int64_t *n_words)

@@ -57,17 +57,6 @@ __device__ __forceinline__ void ex_put_num(char *s, int at, int cap, int x, int 
 
 __device__ __forceinline__ void ex_put(char *s, int at, int cap, char c) { if (at >= 0 && at < cap) s[at] = c; }
 
-__device__ __forceinline__ int ex_nt4(uint8_t c)
-{
-	switch (c) {
-	case 'A': case 'a': return 0;
-	case 'C': case 'c': return 1;
-	case 'G': case 'g': return 2;
-	case 'T': case 't': case 'U': case 'u': return 3;
-	default: return 4;
-	}
-}
-
 __global__ __launch_bounds__(256) void mnc_export_records(Batch B, const int64_t *aln_off, mnc_aln_t *alns, int64_t n_aln)
 {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(256) void mnc_export_strings(Batch B, mnc_aln_t *al
 	auto Q = [&](int p) -> int {                               // column p of the query side, on the hit's strand
 		int at = a.rev ? a.qe - 1 - p : a.qs + p;
 		at = at < 0 ? 0 : at >= qlen ? qlen - 1 : at;
-		const int c = ex_nt4(read[at]);
+		const int c = base_nt4(read[at]);
 		return a.rev ? (c < 4 ? 3 - c : 4) : c;
 	};
 	auto T = [&](int p) -> int {

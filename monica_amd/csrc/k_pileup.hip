@@ -26,28 +26,23 @@
 //                   (each tile places its records behind its offset by a prefix sum over its threads): compacted and in
 //                   (contig, position, allele) order without a per-base offset array.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <new>
 #include <vector>
 #include "device.h"
 #include "scan.h"
-#include "cov_common.h"
+#include "cov_scan.h"
+#include "accum.h"
 
 using namespace mnc;
-
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-	set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-	return e_ == hipErrorOutOfMemory ? MNC_ERR_NOMEM : MNC_ERR_HIP; } } while (0)
 
 static_assert(sizeof(mnc_variant_t) == 20, "mnc_variant_t is 4 int32 and 4 bytes (monica_amd/_capi.py: VARIANT_DTYPE)");
 
 constexpr int PILE_ALT = MNC_PILE_PLANES - 1;   // channels of `alt`: A C G T N DEL INS
 constexpr int CH_N = 4, CH_DEL = 5, CH_INS = 6;
 
-struct mnc_pileup {
-	mnc_index *idx = nullptr;
+struct mnc_pileup : Accum {
 	DeviceIndex *didx = nullptr;               // the index on this device: the reference bases of the read-outs
-	int device = 0, n_contigs = 0;
+	int n_contigs = 0;
 	int64_t n_words = 0;                       // = the index's total_len
 	std::vector<int64_t> off;                  // n_contigs + 1
 	int32_t *track = nullptr;                  // [n_words] depth differences
@@ -56,29 +51,9 @@ struct mnc_pileup {
 	long long *cbase = nullptr;                // [n_contigs] running sum of the track before the contig (scratch)
 	int64_t *tile_sums = nullptr, *tile_cnt = nullptr, *tile_voff = nullptr;   // [n_words / SC_TILE + 2] each (scratch)
 	int64_t *sums2 = nullptr;                  // the scan over tile_cnt's own tile sums (scratch)
-	int64_t bytes = 0;
-	// adds run on the engines' streams, from their threads; reset and the read-outs on this one.  ev_add: the last add
-	// (this stream waits for it); ev_own: the last reset (an add waits for it).  `mu` keeps one thread's record-and-wait
-	// of ev_add in one piece
-	std::mutex mu;
-	hipStream_t st = nullptr;
-	hipEvent_t ev_add = nullptr, ev_own = nullptr;
 };
 
 namespace mnc {
-
-int check_device(int device);                  // engine.hip
-
-__device__ __forceinline__ int pile_nt4(uint8_t c)   // (k_export.hip: ex_nt4)
-{
-	switch (c) {
-	case 'A': case 'a': return 0;
-	case 'C': case 'c': return 1;
-	case 'G': case 'g': return 2;
-	case 'T': case 't': case 'U': case 'u': return 3;
-	default: return 4;
-	}
-}
 
 __device__ __forceinline__ int pile_ref(const uint32_t *seq4, int64_t o)
 {
@@ -97,27 +72,20 @@ __global__ __launch_bounds__(256) void mnc_pile_add(Batch B, int sel, const int6
 	const int lane = lane_id();
 	const uint32_t rd = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
 	if (rd >= B.n_reads) return;                              // (whole waves; the kernel has no workgroup barrier)
-	const int n = B.n_reg[rd];
-	if (n <= 0) return;
-	const int64_t slot0 = reg_slot(B, rd);
-	const int pick = sel == MNC_COV_ASSIGNED ? cov_pick(B, rd, slot0, n) : -1;
-	if (sel == MNC_COV_ASSIGNED && pick < 0) return;
 	const int64_t read_off = B.offsets[rd];
 	const int qlen = (int)(B.offsets[rd + 1] - read_off);
 	if (qlen <= 0) return;
 	const uint8_t *read = B.bases + read_off;
-	for (int i = pick < 0 ? 0 : pick; i < (pick < 0 ? n : pick + 1); ++i) {
-		const mnc_reg_t r = B.regs[slot0 + i];
-		if (!cov_selected(r, sel, B.min_mapq) || r.rid < 0 || r.rid >= n_contigs) continue;
+	cov_for_records(B, rd, sel, n_contigs, [&](const mnc_reg_t &r, int64_t slot) {
 		const int n_c = r.n_cigar;
-		if (n_c <= 0) continue;
+		if (n_c <= 0) return;
 		const int64_t coff = off[r.rid], len = off[r.rid + 1] - coff;
 		int32_t *w = track + coff, *a = alt + coff;            // channel ch of base p: a[ch * n_words + p]
-		const uint32_t *src = B.cig_reg + B.regdp[slot0 + i].cig_off;
+		const uint32_t *src = B.cig_reg + B.regdp[slot].cig_off;
 		auto Q = [&](int p) -> int {                            // column p of the query side, on the hit's strand (k_export.hip)
 			int at = r.rev ? r.qe - 1 - p : r.qs + p;
 			at = at < 0 ? 0 : at >= qlen ? qlen - 1 : at;
-			const int c = pile_nt4(read[at]);
+			const int c = base_nt4(read[at]);
 			return r.rev ? (c < 4 ? 3 - c : 4) : c;
 		};
 		int64_t toff = r.rs;                                   // reference position before the chunk at hand
@@ -132,15 +100,8 @@ __global__ __launch_bounds__(256) void mnc_pile_add(Batch B, int sel, const int6
 			const int cols = op == 1 ? (l > 0) : l;              // an insertion is one column: its bases are not looked at
 			const int it = cov_incl_add(dt), iq = cov_incl_add(dq), ie = cov_incl_add(cols);
 			const int my_t0 = it - dt, my_q0 = qoff + iq - dq;    // (the reference offset within the chunk: toff is 64 bits)
-			// ---- depth: the runs of M columns, as mnc_cov_add_runs opens and closes them
-			const bool is_M = l > 0 && op == 0, is_D = l > 0 && op == 2;
-			const unsigned long long m_M = __ballot(is_M), m_D = __ballot(is_D);
-			const unsigned long long below = (m_M | m_D) & ((1ull << lane) - 1ull);
-			const bool prev_M = below ? (m_M >> (63 - __clzll((long long)below)) & 1ull) != 0 : open;
-			if (is_M && !prev_M) cov_put(w, len, toff + my_t0, 1);
-			if (is_D && prev_M) cov_put(w, len, toff + my_t0, -1);
-			const unsigned long long any = m_M | m_D;
-			if (any) open = (m_M >> (63 - __clzll((long long)any)) & 1ull) != 0;
+			// ---- depth: the runs of M columns
+			cov_run_step(w, len, l > 0 && op == 0, l > 0 && op == 2, toff + my_t0, open);
 			// ---- the columns, one lane each
 			const int total = __shfl(ie, 63);
 			for (int c0 = 0; c0 < total; c0 += 64) {
@@ -166,8 +127,8 @@ __global__ __launch_bounds__(256) void mnc_pile_add(Batch B, int sel, const int6
 			}
 			toff += __shfl(it, 63), qoff += __shfl(iq, 63);
 		}
-		if (open && lane == 0) cov_put(w, len, toff, -1);
-	}
+		cov_run_close(w, len, toff, open);
+	});
 }
 
 // ---------------------------------------------------------------- read-outs
@@ -306,10 +267,7 @@ __global__ __launch_bounds__(SC_THREADS) void mnc_pile_scan(PileView P, int64_t 
 // tile sums of the words [w0, w0 + n) (exclusive, in place) and, for the whole track, the sum in front of every contig
 static void pile_tile_sums(mnc_pileup *pu, int64_t w0, int64_t n, bool all)
 {
-	const int64_t nb = (n + SC_TILE - 1) / SC_TILE;
-	hipLaunchKernelGGL(mnc_scan_reduce<ScanInPlain<int32_t>>, dim3((unsigned)nb), dim3(SC_THREADS), 0, pu->st, ScanInPlain<int32_t>{pu->track + w0}, n, pu->tile_sums);
-	hipLaunchKernelGGL(mnc_scan_sums, dim3(1), dim3(64), 0, pu->st, pu->tile_sums, nb);
-	if (all) hipLaunchKernelGGL(mnc_cov_contig_base, dim3((unsigned)((pu->n_contigs + 3) / 4)), dim3(256), 0, pu->st, pu->track, pu->d_off, pu->n_contigs, pu->tile_sums, pu->cbase);
+	cov_tile_sums(pu->track + w0, n, pu->tile_sums, pu->d_off, pu->n_contigs, all ? pu->cbase : nullptr, pu->st);
 }
 
 template <int MODE>
@@ -321,32 +279,16 @@ static void pile_launch(mnc_pileup *pu, int64_t w0, int64_t n, bool all, int rid
 	                   all ? pu->cbase : nullptr, rid, start, thr, o_counts, pu->tile_cnt, pu->tile_voff, o_var, var_cap, o_cons);
 }
 
-static int pile_interval(const mnc_pileup *pu, int rid, int64_t start, int64_t end)
-{
-	if (rid < 0 || rid >= pu->n_contigs) { set_error("contig %d out of range", rid); return MNC_ERR_ARG; }
-	const int64_t len = pu->off[rid + 1] - pu->off[rid];
-	if (start < 0 || end < start || end > len) {
-		set_error("interval [%lld, %lld) outside contig %d of %lld bases", (long long)start, (long long)end, rid, (long long)len);
-		return MNC_ERR_ARG;
-	}
-	return MNC_OK;
-}
-
 // ---------------------------------------------------------------- the engine's side (mnc_engine_add_pileup, engine.hip)
-const mnc_index *pileup_index(const mnc_pileup *pu) { return pu->idx; }
-int pileup_device_of(const mnc_pileup *pu) { return pu->device; }
+const Accum *as_accum(const mnc_pileup *pu) { return pu; }
 
 // the batch B, as it stands in HBM, on the engine's stream `st`; nothing waits on the host
 int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st)
 {
 	if (B.n_reads == 0 || pu->n_words == 0) return MNC_OK;
-	std::lock_guard<std::mutex> lk(pu->mu);
-	HIP_TRY(hipStreamWaitEvent(st, pu->ev_own, 0));            // behind the last reset
-	hipLaunchKernelGGL(mnc_pile_add, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, pu->d_off, pu->n_contigs, pu->n_words, pu->track, pu->alt);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(pu->ev_add, st));
-	HIP_TRY(hipStreamWaitEvent(pu->st, pu->ev_add, 0));        // reset and the read-outs come after it
-	return MNC_OK;
+	return pu->add(st, [&] {
+		hipLaunchKernelGGL(mnc_pile_add, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, pu->d_off, pu->n_contigs, pu->n_words, pu->track, pu->alt);
+	});
 }
 
 } // namespace mnc
@@ -355,13 +297,7 @@ int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st)
 extern "C" void mnc_pileup_free(mnc_pileup *pu)
 {
 	if (!pu) return;
-	(void)hipSetDevice(pu->device);
-	if (pu->st) (void)hipStreamSynchronize(pu->st);
-	for (void *p : { (void*)pu->track, (void*)pu->alt, (void*)pu->d_off, (void*)pu->cbase, (void*)pu->tile_sums, (void*)pu->tile_cnt, (void*)pu->tile_voff, (void*)pu->sums2 })
-		if (p) (void)hipFree(p);
-	if (pu->ev_add) (void)hipEventDestroy(pu->ev_add);
-	if (pu->ev_own) (void)hipEventDestroy(pu->ev_own);
-	if (pu->st) (void)hipStreamDestroy(pu->st);
+	pu->release();
 	delete pu;
 }
 
@@ -373,38 +309,29 @@ extern "C" int mnc_pileup_create(mnc_index *idx, int device, mnc_pileup **out)
 	if (idx->seq_off.size() != idx->contig_len.size() + 1) { set_error("the index holds no contig bases"); return MNC_ERR_ARG; }
 	mnc_pileup *pu = new (std::nothrow) mnc_pileup;
 	if (!pu) return MNC_ERR_NOMEM;
-	pu->idx = idx, pu->device = device, pu->n_contigs = (int)idx->contig_len.size();
+	pu->n_contigs = (int)idx->contig_len.size();
 	try {
 		pu->off.assign(idx->seq_off.begin(), idx->seq_off.end());   // the planes' layout is the 4-bit store's
 	} catch (const std::bad_alloc &) { delete pu; return MNC_ERR_NOMEM; }
 	pu->n_words = pu->off[pu->n_contigs];
 	if (int rc = index_upload(idx, device, &pu->didx)) { delete pu; return rc; }
 	const size_t nc = (size_t)pu->n_contigs, nw = (size_t)pu->n_words, nt = nw / SC_TILE + 2;
-	hipError_t he = hipSetDevice(device);
-	auto alloc = [&](void **p, size_t bytes) {
-		if (he != hipSuccess) return;
-		bytes = bytes ? bytes : 8;
-		he = hipMalloc(p, bytes);
-		if (he == hipSuccess) pu->bytes += (int64_t)bytes; else *p = nullptr;
-	};
-	alloc((void**)&pu->track, nw * 4);
-	alloc((void**)&pu->alt, nw * 4 * PILE_ALT);
-	alloc((void**)&pu->d_off, (nc + 1) * 8);
-	alloc((void**)&pu->cbase, nc * 8);
-	alloc((void**)&pu->tile_sums, nt * 8);
-	alloc((void**)&pu->tile_cnt, nt * 8);
-	alloc((void**)&pu->tile_voff, nt * 8);
-	alloc((void**)&pu->sums2, (nt / SC_TILE + 2) * 8);
-	const bool nomem = he == hipErrorOutOfMemory;
-	if (he == hipSuccess) he = hipStreamCreateWithFlags(&pu->st, hipStreamNonBlocking);
-	if (he == hipSuccess) he = hipEventCreateWithFlags(&pu->ev_add, hipEventDisableTiming);
-	if (he == hipSuccess) he = hipEventCreateWithFlags(&pu->ev_own, hipEventDisableTiming);
+	hipError_t he = pu->begin(idx, device);
+	pu->alloc(he, (void**)&pu->track, nw * 4);
+	pu->alloc(he, (void**)&pu->alt, nw * 4 * PILE_ALT);
+	pu->alloc(he, (void**)&pu->d_off, (nc + 1) * 8);
+	pu->alloc(he, (void**)&pu->cbase, nc * 8);
+	pu->alloc(he, (void**)&pu->tile_sums, nt * 8);
+	pu->alloc(he, (void**)&pu->tile_cnt, nt * 8);
+	pu->alloc(he, (void**)&pu->tile_voff, nt * 8);
+	pu->alloc(he, (void**)&pu->sums2, (nt / SC_TILE + 2) * 8);
+	pu->streams(he);
 	if (he == hipSuccess) he = hipMemcpy(pu->d_off, pu->off.data(), (nc + 1) * 8, hipMemcpyHostToDevice);
 	if (he != hipSuccess) {
 		set_error("pileup accumulator of %lld bases (32 bytes each): %s", (long long)pu->n_words, hipGetErrorString(he));
-		(void)hipGetLastError();
+		const int rc = Accum::failed(he);
 		mnc_pileup_free(pu);
-		return nomem ? MNC_ERR_NOMEM : MNC_ERR_HIP;
+		return rc;
 	}
 	if (int rc = mnc_pileup_reset(pu)) { mnc_pileup_free(pu); return rc; }
 	*out = pu;
@@ -420,16 +347,11 @@ extern "C" int mnc_pileup_reset(mnc_pileup *pu)
 		HIP_TRY(hipMemsetAsync(pu->track, 0, (size_t)pu->n_words * 4, pu->st));
 		HIP_TRY(hipMemsetAsync(pu->alt, 0, (size_t)pu->n_words * 4 * PILE_ALT, pu->st));
 	}
-	HIP_TRY(hipEventRecord(pu->ev_own, pu->st));
+	HIP_TRY(pu->own_done());
 	return MNC_OK;
 }
 
-extern "C" int mnc_pileup_device_bytes(const mnc_pileup *pu, int64_t *bytes)
-{
-	if (!pu || !bytes) return MNC_ERR_ARG;
-	*bytes = pu->bytes;
-	return MNC_OK;
-}
+extern "C" int mnc_pileup_device_bytes(const mnc_pileup *pu, int64_t *bytes) { return accum_device_bytes(pu, bytes); }
 
 extern "C" int mnc_pileup_device(mnc_pileup *pu, const int32_t **d_depth, const int32_t **d_alt, int64_t *n_words)
 {
@@ -440,22 +362,10 @@ extern "C" int mnc_pileup_device(mnc_pileup *pu, const int32_t **d_depth, const 
 	return MNC_OK;
 }
 
-// what a read-out leaves on the host: `bytes` of the device buffer `tmp`, behind the kernels queued on the accumulator's stream
-static int pile_finish(mnc_pileup *pu, void *dst, void *tmp, size_t bytes, const char *what)
-{
-	hipError_t he = hipGetLastError();
-	if (he == hipSuccess) he = hipMemcpyAsync(dst, tmp, bytes, hipMemcpyDeviceToHost, pu->st);
-	const hipError_t hs = hipStreamSynchronize(pu->st);
-	if (he == hipSuccess) he = hs;
-	(void)hipFree(tmp);
-	if (he != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(he)); return MNC_ERR_HIP; }
-	return MNC_OK;
-}
-
 extern "C" int mnc_pileup_fetch_counts(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t *out)
 {
 	if (!pu) return MNC_ERR_ARG;
-	if (int rc = pile_interval(pu, rid, start, end)) return rc;
+	if (int rc = accum_interval(pu->off, rid, start, end)) return rc;
 	if (end == start) return MNC_OK;
 	if (!out) return MNC_ERR_ARG;
 	HIP_TRY(hipSetDevice(pu->device));
@@ -464,13 +374,13 @@ extern "C" int mnc_pileup_fetch_counts(mnc_pileup *pu, int rid, int64_t start, i
 	HIP_TRY(hipMalloc((void**)&tmp, bytes));
 	pile_tile_sums(pu, pu->off[rid], end, false);               // the contig's words up to `end`: the sum starts at the contig
 	pile_launch<0>(pu, pu->off[rid], end, false, rid, start, PileThr{0, 0, 0}, tmp, nullptr, 0, nullptr);
-	return pile_finish(pu, out, tmp, bytes, "pileup counts");
+	return pu->finish(hipSuccess, tmp, {out, tmp, bytes}, {}, "pileup counts");
 }
 
 extern "C" int mnc_pileup_consensus(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t min_depth, char *out)
 {
 	if (!pu) return MNC_ERR_ARG;
-	if (int rc = pile_interval(pu, rid, start, end)) return rc;
+	if (int rc = accum_interval(pu->off, rid, start, end)) return rc;
 	if (end == start) return MNC_OK;
 	if (!out) return MNC_ERR_ARG;
 	HIP_TRY(hipSetDevice(pu->device));
@@ -478,7 +388,7 @@ extern "C" int mnc_pileup_consensus(mnc_pileup *pu, int rid, int64_t start, int6
 	HIP_TRY(hipMalloc((void**)&tmp, (size_t)(end - start)));
 	pile_tile_sums(pu, pu->off[rid], end, false);
 	pile_launch<3>(pu, pu->off[rid], end, false, rid, start, PileThr{min_depth, 0, 0}, nullptr, nullptr, 0, tmp);
-	return pile_finish(pu, out, tmp, (size_t)(end - start), "pileup consensus");
+	return pu->finish(hipSuccess, tmp, {out, tmp, (size_t)(end - start)}, {}, "pileup consensus");
 }
 
 extern "C" int mnc_pileup_call_variants(mnc_pileup *pu, int rid, int32_t min_depth, int32_t min_count, int32_t min_permille, mnc_variant_t *out, int64_t cap, int64_t *n)
@@ -509,5 +419,5 @@ extern "C" int mnc_pileup_call_variants(mnc_pileup *pu, int rid, int32_t min_dep
 	mnc_variant_t *tmp = nullptr;
 	HIP_TRY(hipMalloc((void**)&tmp, (size_t)total * sizeof(mnc_variant_t)));
 	pile_launch<2>(pu, w0, len, all, rid, 0, thr, nullptr, tmp, total, nullptr);
-	return pile_finish(pu, out, tmp, (size_t)total * sizeof(mnc_variant_t), "pileup variants");
+	return pu->finish(hipSuccess, tmp, {out, tmp, (size_t)total * sizeof(mnc_variant_t)}, {}, "pileup variants");
 }

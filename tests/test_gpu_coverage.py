@@ -5,6 +5,7 @@ Reference: tests/covref.py -- the contract in plain numpy -- applied to the CPU 
 plain-Python best_hit for the selectors.  Nothing is compared against the engine's export or dumps."""
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 import pytest
@@ -166,6 +167,42 @@ def test_accumulation_reset_and_a_second_engine(capi, world, corpus):
     other.add_coverage(cov, what)                               # and on after a reset
     check(cov, want)
     other.close()
+    cov.close()
+
+
+@pytest.mark.parametrize("span", [0, covref.SPAN])
+def test_two_engines_on_threads_add_into_one_coverage(capi, world, corpus, span):
+    """test_gpu_pileup.py's test_two_engines_on_threads_add_into_one_pileup for the coverage accumulator: an add is one
+    piece against another thread's, for either kernel."""
+    off = corpus["offsets"]
+    cut = len(corpus["reads"]) // 2
+    what = capi.COV_ALL | span
+    cov = capi.Coverage(world.idx, 0, 1000)
+    halves = [(corpus["bases"][:off[cut]], off[:cut + 1]), (corpus["bases"][off[cut]:], off[cut:] - off[cut])]
+    errors = []
+
+    def work(bases, offsets):
+        try:
+            eng = capi.Engine(world.idx, 0)
+            eng.classify(bases, offsets, MIN_MAPQ)
+            eng.add_coverage(cov, what)
+            eng.sync()
+            eng.close()
+        except Exception as err:                                  # noqa: BLE001 -- reported below, on the main thread
+            errors.append(err)
+
+    threads = [threading.Thread(target=work, args=h) for h in halves]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    want = world.want("corpus", corpus["ref"], what)
+    check(cov, want)
+    cov.reset()                                                 # and a reset behind them: one add gives the single answer again
+    world.eng.classify(corpus["bases"], corpus["offsets"], MIN_MAPQ)
+    world.eng.add_coverage(cov, what)
+    check(cov, want)
     cov.close()
 
 

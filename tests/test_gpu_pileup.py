@@ -241,6 +241,40 @@ def test_two_engines_on_threads_add_into_one_pileup(capi, world, corpus):
     pu.close()
 
 
+# ---------------------------------------------------------------- 3b. the walk shared with the coverage accumulator
+def test_a_cigar_longer_than_two_chunks(capi, world):
+    """test_gpu_coverage.py's reads of the same name: the run carried across a chunk border, together with the query and
+    reference offsets carried beside it."""
+    rng = np.random.default_rng(66)
+    g = world.clean[1]
+    reads = [mutate(rng, g[5_000:11_000], sub=0.04, ins=0.04, dele=0.04), util.revcomp(mutate(rng, g[30_000:36_000], sub=0.04, ins=0.04, dele=0.04))]
+    ref = world.oracle_dp(reads)
+    assert all(len(r) >= 1 for r, _ in ref) and all(len(c[0]) > 128 for _, c in ref), "CIGARs of more than 128 operations"
+    world.eng.classify(*util.pack_reads(reads), 0)
+    pu = capi.Pileup(world.idx, 0)
+    world.eng.add_pileup(pu, capi.COV_ALL)
+    check(pu, world.want("long cigar", ref, reads, capi.COV_ALL, 0))
+    pu.close()
+
+
+def test_coverage_and_pileup_of_the_same_adds_agree_on_depth(capi, world, corpus):
+    n = 40
+    off = corpus["offsets"][:n + 1]
+    world.eng.classify(corpus["bases"][:off[-1]], off, MIN_MAPQ)
+    pu, cov = capi.Pileup(world.idx, 0), capi.Coverage(world.idx, 0, 1024)
+    for sel in SELECTORS:
+        pu.reset(), cov.reset()
+        world.eng.add_pileup(pu, sel)
+        world.eng.add_coverage(cov, sel)
+        total = 0
+        for rid in range(len(LENS)):
+            depth = cov.depth(rid)
+            assert np.array_equal(depth, pu.counts(rid)[0]), f"selector {sel}, contig {rid}"
+            total += int(depth.sum())
+        assert total > 0, f"selector {sel}: nothing was added"
+    pu.close(), cov.close()
+
+
 # ---------------------------------------------------------------- 4. variants and consensus
 def test_variants_and_consensus_equal_the_reference(capi, world, corpus):
     L = capi.lib()
