@@ -195,6 +195,10 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   a candidate row beyond cap_cands             not stored and counted in n_dropped; mnc_abundance_solve: MNC_ERR_RANGE until
  *                                                mnc_abundance_reset
  *   a read that fits more than six genomes       sees six: a region list holds a primary and best_n = 5 secondaries
+ *   carried candidates after a call that ran     mnc_engine_carry_candidates: MNC_ERR_UNSUPPORTED, the carry untouched (as for
+ *   both the usual and the wide pass             mnc_engine_add_abundance); MNC_ERR_ARG under MNC_CONTRACT_CHAIN
+ *   a read with more than `width` candidates     the `width` ranked highest stay (score descending, ties to the smaller genome
+ *   within max_delta, over all parts             id); the read is counted in n_truncated_reads of mnc_carry_info
  */
 
 /* ---------------------------------------------------------------- classify
@@ -639,7 +643,7 @@ int  mnc_abundance_device_bytes(const mnc_abundance *ab, int64_t *bytes);
 int  mnc_engine_add_abundance(mnc_engine *eng, mnc_abundance *ab);
 /* Adds rows made by the caller -- row r = (genome, delta)[offsets[r] .. offsets[r + 1]) -- with the same treatment: a row of
  * one candidate goes to unique, a row of two or more is stored; n_reads grows by n_reads.  For a caller who merges the
- * parts of a multi-part database itself (that needs read identity, which the library does not carry here).  Checked on the
+ * parts of a multi-part database itself (the library's own way is the candidate carry below).  Checked on the
  * host before anything is touched: MNC_ERR_ARG for an empty row, genome ids not strictly ascending within a row, a genome
  * id >= G or negative, a delta negative or above max_delta; MNC_ERR_RANGE when the rows would not fit -- nothing is added
  * then and n_dropped stays as it was.  Waits for the work queued so far. */
@@ -658,6 +662,95 @@ int  mnc_abundance_solve(mnc_abundance *ab, int32_t max_iter, uint64_t tol_q32, 
  * d_offsets int64[n_stored_reads + 1], d_genome / d_delta int32[n_cands].  Ordered behind the adds only after a read-out
  * call above or a sync of the engines that added. */
 int  mnc_abundance_device(mnc_abundance *ab, const int64_t **d_unique, const int64_t **d_offsets, const int32_t **d_genome, const int32_t **d_delta);
+
+/* ---------------------------------------------------------------- candidate carry
+ * Abundance over a database of SEVERAL index parts.  Close strains land in different parts, and a read's candidate genomes
+ * have to be put together across them: that needs read identity, and a merge that does not depend on the order of the parts
+ * or on how the reads were cut into batches.  An mnc_carry is both.  It belongs to a device, not to an index, and holds one
+ * row per read of a sample, addressed by the read's ordinal in the sample (the sample file is the same for every part).  A
+ * row is: best, the largest score seen for this read in any part so far; up to `width` pairs (global genome id, score); and
+ * a sticky "truncated" bit.  8 * width + 8 bytes of HBM per read.  Every part's batches are carried into it from HBM as
+ * they stand (mnc_engine_carry_candidates; csrc/k_carry.hip), and after the last part mnc_abundance_add_carry hands every
+ * row to an accumulator made for the genomes of the whole database (mnc_abundance_create_global).  Runs only when asked
+ * for: a batch that does not ask costs not one more kernel, allocation or byte.
+ *
+ * The merge rule.
+ * 1. What one part gives a read.  For every genome g of the part with at least one counted record, s_g = the largest dp_max
+ *    of the read's records on contigs of g.  A counted record is one that mnc_engine_add_abundance counts: of the set
+ *    MNC_COV_ALL walks, with a CIGAR, on a contig of the index.  The part offers the pairs (g + genome_offset, s_g).  Only
+ *    pairs within max_delta of the part's own best need be offered (the implementation passes over the others): that loses
+ *    nothing, because the global best is at least the part's best.  A read with no counted record offers nothing and its
+ *    row stays as it is.
+ * 2. The incoming row.  best := max(best, the incoming scores).
+ * 3. Merging into a row.  A genome already in the row keeps the larger of its two scores.  Then every pair with
+ *    best - score > max_delta leaves.  If more than `width` pairs remain, the `width` pairs ranked highest stay -- ranking
+ *    is by score descending, with ties going to the smaller genome id -- and the read's truncated bit is set.
+ * 4. Consequences.  The final row is the top `width` pairs by that ranking among all pairs ever offered (per genome its
+ *    largest score), cut at best - max_delta.  The operation is commutative, associative and idempotent, so the rows do not
+ *    depend on the order of the parts, on how each part's reads were cut into batches, on which of the three entry points
+ *    (mnc_engine_carry_candidates, mnc_carry_add_lists, mnc_carry_merge) delivered a pair, or on a part being carried
+ *    twice.  Only n_truncated_reads may depend on the order: a pair can leave by the delta cut in one order and for room
+ *    in another.  (mnc_carry_merge also hands on the source row's truncated bit.)
+ *
+ * Ordering and threading.  A carry's merges run one behind the other on the device: each waits for the previous merge's
+ * event, whichever engine queued it, so engines may carry into one mnc_carry from their own threads -- by the property
+ * above the result is the same.  Reset, reserve, add_lists, merge as dst, and the read-outs are for one thread at a time.
+ * Nothing on the engine's stream waits on the host.  Every error leaves the carry untouched. */
+typedef struct mnc_carry mnc_carry;
+/* MNC_ERR_ARG: cap_reads < 0 (or > 2^32), width outside 1 .. 64 (a row lives in one wave of 64 lanes), max_delta < 0 -- all
+ * checked before the device.  MNC_ERR_NODEVICE without a gfx950 device, MNC_ERR_NOMEM when HBM is short.  The Python
+ * layer's defaults: width = 16, max_delta = 80. */
+int  mnc_carry_create(int device, int64_t cap_reads, int32_t width /* 1..64 */, int32_t max_delta, mnc_carry **out);
+/* frees the carry and the HBM it holds (waits for the work queued on it) */
+void mnc_carry_free(mnc_carry *cc);
+/* every row empty; asynchronous */
+int  mnc_carry_reset(mnc_carry *cc);
+/* grows to >= n_reads rows (by half as much again at least); contents kept, new rows empty.  Waits for the merges queued so
+ * far when it has to grow; not while an engine carries.  MNC_ERR_NOMEM leaves the carry as it was. */
+int  mnc_carry_reserve(mnc_carry *cc, int64_t n_reads);
+/* HBM the carry holds: 8 * width + 8 bytes per row */
+int  mnc_carry_device_bytes(const mnc_carry *cc, int64_t *bytes);
+/* Merges the last classified batch of `eng`, as it stands in HBM, into rows first_read .. first_read + n_reads - 1: read r of
+ * the batch is read first_read + r of the sample, genome g of the engine's index is genome genome_offset + g.  Asynchronous
+ * on the engine's stream behind the carry's earlier merges, no host wait.  MNC_ERR_ARG: first_read < 0, genome_offset < 0,
+ * genome_offset + the index's genomes beyond int32, a carry on another device than the engine's, no batch classified yet,
+ * MNC_CONTRACT_CHAIN (no dp_max).  MNC_ERR_UNSUPPORTED: the last call ran both the usual and the wide pass, as for
+ * mnc_engine_add_abundance.  MNC_ERR_RANGE: first_read + n_reads > cap_reads (mnc_carry_reserve first). */
+int  mnc_engine_carry_candidates(mnc_engine *eng, mnc_carry *cc, int64_t first_read, int32_t genome_offset);
+/* Host rows -- row r = (genome, score)[offsets[r] .. offsets[r + 1]), global genome ids -- merged by the same rule; row r goes
+ * to read first_read + r.  Checked on the host before anything is touched: MNC_ERR_ARG for first_read < 0, an empty row,
+ * genome ids negative or not strictly ascending within a row; MNC_ERR_RANGE for first_read + n_reads > cap_reads.  Waits. */
+int  mnc_carry_add_lists(mnc_carry *cc, int64_t first_read, int64_t n_reads, const int64_t *offsets,
+                         const int32_t *genome, const int32_t *score);
+/* src's rows merged into dst's, row for row, by the same rule; src is left as it is.  MNC_ERR_ARG unless both are on one
+ * device with one width and one max_delta; MNC_ERR_RANGE when src has more rows than dst.  Asynchronous. */
+int  mnc_carry_merge(mnc_carry *dst, mnc_carry *src);
+/* the counts as they stand (waits for the merges queued so far); any pointer may be NULL.  n_rows_used = rows that hold a
+ * pair, n_cands = pairs held, n_truncated_reads = rows whose truncated bit is set */
+int  mnc_carry_info(mnc_carry *cc, int64_t *cap_reads, int64_t *n_rows_used, int64_t *n_cands, int64_t *n_truncated_reads);
+/* rows first_read .. first_read + n_reads - 1 (waits): count[r] pairs, best[r] (0 for an empty row), and the pairs in
+ * ASCENDING GENOME ID in genome / score [n_reads][width], unused places -1 / 0.  Any out pointer may be NULL.
+ * MNC_ERR_RANGE beyond cap_reads. */
+int  mnc_carry_fetch(mnc_carry *cc, int64_t first_read, int64_t n_reads, int32_t *count, int32_t *best,
+                     int32_t *genome, int32_t *score /* [n_reads][width], ascending genome id, unused slots -1 / 0 */);
+/* The raw rows in place, for a collective of the caller's (gather them, then mnc_carry_add_lists or a carry of one's own and
+ * mnc_carry_merge): d_head int32[cap_reads][2] = (best, flags: 1 the row holds a pair, 2 truncated); d_slots
+ * int32[cap_reads][width][2] = (genome, score) in NO particular order, a free slot (-1, 0).  Any out pointer may be NULL.
+ * Ordered behind the merges only after a read-out call above or a sync of the engines that carried; the pointers change
+ * when mnc_carry_reserve grows the carry. */
+int  mnc_carry_device(mnc_carry *cc, const int32_t **d_head, const int32_t **d_slots, int64_t *cap_reads, int32_t *width);
+
+/* An abundance accumulator that is not tied to one index: mnc_abundance_create with G = n_genomes and no index, for the
+ * genomes of a whole database in part order.  mnc_engine_add_abundance answers MNC_ERR_ARG for it (it is for no index);
+ * add_lists, add_carry, the read-outs and solve work on it.  MNC_ERR_ARG also for n_genomes < 0. */
+int  mnc_abundance_create_global(int device, int32_t n_genomes, int64_t cap_cands, int32_t max_delta, int32_t scale_q, mnc_abundance **out);
+/* The carry's rows first_read .. first_read + n_reads - 1, each treated exactly as mnc_engine_add_abundance treats a read: no
+ * pair, nothing; one pair, unique[g] += 1; two or more, one stored row of (genome, best - score) in ascending genome id, or
+ * -- when it does not fit -- counted in n_dropped.  MNC_ERR_ARG, nothing added: the carry's max_delta differs from the
+ * accumulator's, the device differs, or the carry holds a genome id >= G (its largest id is read back first: the one host
+ * wait, for the carry's merges).  MNC_ERR_RANGE: first_read + n_reads > cap_reads.  The add itself is asynchronous on the
+ * accumulator's stream behind the carry's merges.  The carry is left as it is. */
+int  mnc_abundance_add_carry(mnc_abundance *ab, mnc_carry *cc, int64_t first_read, int64_t n_reads);
 
 /* ---------------------------------------------------------------- FASTQ batches and read routing
  * Replaces the per-record Biopython objects of the reference's loop:

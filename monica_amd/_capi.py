@@ -88,7 +88,9 @@ EXPORTS = [
     "mnc_pileup_fetch_counts", "mnc_pileup_call_variants", "mnc_pileup_consensus",
     "mnc_abundance_create", "mnc_abundance_free", "mnc_abundance_reset", "mnc_abundance_device_bytes", "mnc_engine_add_abundance",
     "mnc_abundance_add_lists", "mnc_abundance_info", "mnc_abundance_fetch_unique", "mnc_abundance_fetch_lists", "mnc_abundance_solve",
-    "mnc_abundance_device",
+    "mnc_abundance_device", "mnc_abundance_create_global", "mnc_abundance_add_carry",
+    "mnc_carry_create", "mnc_carry_free", "mnc_carry_reset", "mnc_carry_reserve", "mnc_carry_device_bytes", "mnc_engine_carry_candidates",
+    "mnc_carry_add_lists", "mnc_carry_merge", "mnc_carry_info", "mnc_carry_fetch", "mnc_carry_device",
 ]
 
 
@@ -249,6 +251,19 @@ def lib():
     sig("mnc_abundance_fetch_lists", i32, [vp, vp, vp, vp, i64, i64])
     sig("mnc_abundance_solve", i32, [vp, C.c_int32, u64, vp, vp, C.POINTER(C.c_int32)])
     sig("mnc_abundance_device", i32, [vp, pp, pp, pp, pp])
+    sig("mnc_abundance_create_global", i32, [i32, C.c_int32, i64, C.c_int32, C.c_int32, pp])
+    sig("mnc_abundance_add_carry", i32, [vp, vp, i64, i64])
+    sig("mnc_carry_create", i32, [i32, i64, C.c_int32, C.c_int32, pp])
+    sig("mnc_carry_free", None, [vp])
+    sig("mnc_carry_reset", i32, [vp])
+    sig("mnc_carry_reserve", i32, [vp, i64])
+    sig("mnc_carry_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_engine_carry_candidates", i32, [vp, vp, i64, C.c_int32])
+    sig("mnc_carry_add_lists", i32, [vp, i64, i64, vp, vp, vp])
+    sig("mnc_carry_merge", i32, [vp, vp])
+    sig("mnc_carry_info", i32, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)])
+    sig("mnc_carry_fetch", i32, [vp, i64, i64, vp, vp, vp, vp])
+    sig("mnc_carry_device", i32, [vp, pp, pp, C.POINTER(i64), C.POINTER(C.c_int32)])
     _LIB = L
     return L
 
@@ -591,6 +606,11 @@ class Engine:
         HBM, to the accumulator `abundance`.  Asynchronous."""
         self._add("mnc_engine_add_abundance", abundance)
 
+    def carry_candidates(self, carry, first_read, genome_offset):
+        """`mnc_engine_carry_candidates`: merge the candidate genomes of every read of the last classified batch into the
+        rows `first_read ..` of `carry`; genome g of this engine's index is genome `genome_offset` + g there.  Asynchronous."""
+        self._add("mnc_engine_carry_candidates", carry, int(first_read), int(genome_offset))
+
     def _add(self, symbol, acc, *args):
         check(getattr(lib(), symbol)(self._h, acc._h if acc is not None else None, *args))
 
@@ -801,7 +821,7 @@ class Abundance(_Accumulator):
 
     _c = "abundance"
 
-    def __init__(self, index, device=0, cap_cands=ABUNDANCE_CAP_CANDS, max_delta=ABUNDANCE_MAX_DELTA, scale_q=ABUNDANCE_SCALE_Q):
+    def __init__(self, index, device=0, cap_cands=ABUNDANCE_CAP_CANDS, max_delta=ABUNDANCE_MAX_DELTA, scale_q=ABUNDANCE_SCALE_Q, n_genomes=None):
         cap_cands, max_delta, scale_q = int(cap_cands), int(max_delta), int(scale_q)
         if cap_cands < 0:
             raise ValueError(f"cap_cands = {cap_cands}: a number of candidate slots")
@@ -812,7 +832,37 @@ class Abundance(_Accumulator):
         self.device = device
         self.cap_cands, self.max_delta, self.scale_q = cap_cands, max_delta, scale_q
         self.n_genomes = len(index.genome_names) if index is not None else 0
-        self._create(index, device, cap_cands, max_delta, scale_q)
+        self.genome_names = list(index.genome_names) if index is not None else []
+        if n_genomes is None:
+            self._create(index, device, cap_cands, max_delta, scale_q)
+            return
+        # for the genomes of a whole database, of no index: `global_`
+        if index is not None or int(n_genomes) < 0:
+            raise ValueError(f"n_genomes = {n_genomes}: a number of genomes, and no index beside it")
+        self.n_genomes = int(n_genomes)
+        h = C.c_void_p()
+        check(lib().mnc_abundance_create_global(int(device), self.n_genomes, cap_cands, max_delta, scale_q, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def global_(cls, device, n_genomes, cap_cands=ABUNDANCE_CAP_CANDS, max_delta=ABUNDANCE_MAX_DELTA, scale_q=ABUNDANCE_SCALE_Q, genome_names=None):
+        """`mnc_abundance_create_global`: an accumulator for `n_genomes` genomes that is tied to no index -- the genomes of a
+        database of several parts, in part order.  It is added to by `add_carry` and `add_lists`; `Engine.add_abundance`
+        refuses it.  `genome_names` (optional) is kept for whoever writes the result out."""
+        ab = cls(None, device, cap_cands, max_delta, scale_q, n_genomes=n_genomes)
+        if genome_names is not None:
+            if len(genome_names) != ab.n_genomes:
+                ab.close()
+                raise ValueError(f"{len(genome_names)} genome names for {ab.n_genomes} genomes")
+            ab.genome_names = list(genome_names)
+        return ab
+
+    def add_carry(self, carry, first_read=0, n_reads=None):
+        """`mnc_abundance_add_carry`: rows `first_read .. first_read + n_reads - 1` of the candidate carry `carry` (default: to
+        its end), each as one read.  The carry is left as it is."""
+        if n_reads is None:
+            n_reads = carry.info()["cap_reads"] - int(first_read)
+        check(lib().mnc_abundance_add_carry(self._h, carry._h if carry is not None else None, int(first_read), int(n_reads)))
 
     def add_lists(self, offsets, genome, delta):
         """Rows made by the caller: row r is (genome, delta)[offsets[r]:offsets[r + 1]], genome ids ascending.  A row of one
@@ -863,6 +913,75 @@ class Abundance(_Accumulator):
         p = [C.c_void_p() for _ in range(4)]
         check(lib().mnc_abundance_device(self._h, *[C.byref(x) for x in p]))
         return tuple(int(x.value or 0) for x in p)
+
+
+# ---------------------------------------------------------------------------------- candidate carry
+CARRY_WIDTH = 16                        # pairs per read when the caller names none: 136 bytes of HBM a read
+CARRY_MAX_WIDTH = 64                    # a row lives in one wave, one pair per lane
+
+
+class Carry(_Accumulator):
+    """Owner of an ``mnc_carry``: one row per read of a sample -- the best score any index part has given the read and up
+    to `width` (global genome id, score) pairs -- merged into from every part's batches by `Engine.carry_candidates` and
+    handed to a global `Abundance` by `Abundance.add_carry` (include/monica_amd.h, "candidate carry").  It belongs to a
+    device, not to an index."""
+
+    _c = "carry"
+
+    def __init__(self, device, cap_reads, width=CARRY_WIDTH, max_delta=ABUNDANCE_MAX_DELTA):
+        cap_reads, width, max_delta = int(cap_reads), int(width), int(max_delta)
+        if cap_reads < 0:
+            raise ValueError(f"cap_reads = {cap_reads}: a number of reads")
+        if not 1 <= width <= CARRY_MAX_WIDTH:
+            raise ValueError(f"width = {width}: 1 .. {CARRY_MAX_WIDTH} pairs per read")
+        if max_delta < 0:
+            raise ValueError(f"max_delta = {max_delta}: max_delta >= 0 is required")
+        self.device, self.width, self.max_delta = int(device), width, max_delta
+        h = C.c_void_p()
+        check(lib().mnc_carry_create(self.device, cap_reads, width, max_delta, C.byref(h)))
+        self._h = h
+
+    def reserve(self, n_reads):
+        """Grow to at least `n_reads` rows; contents kept, new rows empty."""
+        check(lib().mnc_carry_reserve(self._h, int(n_reads)))
+
+    def info(self):
+        """{"cap_reads", "n_rows_used", "n_cands", "n_truncated_reads"} as they stand (waits for the merges queued so far)."""
+        v = [C.c_int64(0) for _ in range(4)]
+        check(lib().mnc_carry_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("cap_reads", "n_rows_used", "n_cands", "n_truncated_reads"), (int(x.value) for x in v)))
+
+    def fetch(self, first_read=0, n_reads=None):
+        """Rows `first_read .. first_read + n_reads - 1` (default: to the end): (count int32[n], best int32[n], genome
+        int32[n, width], score int32[n, width]); a row's pairs in ascending genome id, unused places -1 / 0."""
+        if n_reads is None:
+            n_reads = self.info()["cap_reads"] - int(first_read)
+        n = max(int(n_reads), 0)
+        count, best = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        genome, score = np.zeros((n, self.width), dtype=np.int32), np.zeros((n, self.width), dtype=np.int32)
+        check(lib().mnc_carry_fetch(self._h, int(first_read), int(n_reads), *[a.ctypes.data if a.size else None for a in (count, best, genome, score)]))
+        return count, best, genome, score
+
+    def add_lists(self, first_read, offsets, genome, score):
+        """Rows made by the caller: row r is (genome, score)[offsets[r]:offsets[r + 1]], global genome ids ascending, merged
+        into read `first_read` + r by the carry's rule."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        genome = np.ascontiguousarray(genome, dtype=np.int32)
+        score = np.ascontiguousarray(score, dtype=np.int32)
+        if offsets.ndim != 1 or len(offsets) < 1 or len(genome) != len(score) or (len(offsets) > 1 and int(offsets[-1]) > len(genome)):
+            raise ValueError("offsets holds n_reads + 1 entries into genome / score, which have one length")
+        check(lib().mnc_carry_add_lists(self._h, int(first_read), len(offsets) - 1, offsets.ctypes.data, genome.ctypes.data if len(genome) else None,
+                                        score.ctypes.data if len(score) else None))
+
+    def merge(self, src):
+        """`mnc_carry_merge`: the rows of `src` merged into this carry's, row for row; `src` is left as it is."""
+        check(lib().mnc_carry_merge(self._h, src._h if src is not None else None))
+
+    def device_rows(self):
+        """(device address of the heads, of the slots, cap_reads, width): `mnc_carry_device`."""
+        h, s, n, w = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int32(0)
+        check(lib().mnc_carry_device(self._h, C.byref(h), C.byref(s), C.byref(n), C.byref(w)))
+        return int(h.value or 0), int(s.value or 0), int(n.value), int(w.value)
 
 
 # ---------------------------------------------------------------------------------- host helpers

@@ -70,7 +70,8 @@ COVERAGE_CSV_HEADER = ("genome", "contig", "length", "covered_bases", "breadth",
 PILEUP_THRESHOLDS = (5, 3, 500)
 VARIANTS_TSV_HEADER = ("genome", "contig", "pos", "ref", "alt", "count", "span", "permille")
 # `abundance=True`: the accumulator's defaults (`_capi.Abundance`); a dict of cap_cands / max_delta / scale_q / max_iter /
-# tol_q32 in its place sets its own
+# tol_q32 in its place sets its own.  {"across_parts": True, ...} takes a database of several index parts: every read's
+# candidates are carried from part to part on the device (`_capi.Carry`, "width" pairs per read)
 ABUNDANCE_CSV_HEADER = ("genome", "theta", "expected_reads", "unique_reads")
 ABUNDANCE_MULTI_PART = ("abundance= needs a database of ONE index part: a read's candidate genomes would have to be merged across "
                         "the parts, which needs read identity -- merge them yourself and hand the rows to Abundance.add_lists")
@@ -136,7 +137,8 @@ def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quali
     """Classify every non-empty `*fastq` file of `query_folder` against the index parts
     (aligner.py:65-111): every part but the last only collects hits; the last part decides.
     `abundance`, `coverage`, `pileup` (not in the reference; off by default): see `aligner_coverage`."""
-    if abundance and len(indexes_paths) != 1:
+    across = isinstance(abundance, dict) and bool(abundance.get("across_parts")) and len(indexes_paths) > 1
+    if abundance and len(indexes_paths) != 1 and not across:
         raise ValueError(ABUNDANCE_MULTI_PART)
     os.chdir(query_folder)
     samples = [f for f in os.listdir(".") if f.endswith("fastq") and os.stat(f).st_size]
@@ -164,7 +166,11 @@ def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quali
     pool = ThreadPool(workers)
     rep = itertools.repeat
     mappy.reserve_index_cache(len(indexes_paths))
-    extra = [rep(abundance), rep(coverage), rep(pileup)] if abundance or coverage or pileup else []     # the arguments `aligner` does not have
+    # across parts: one carry per sample for the length of this call (in HBM, made by the first part's run, never pickled),
+    # the genome names of the parts so far (their number is the next part's genome offset) -- handed on in the sample's dict
+    carried = [{"carry": None, "names": []} for _ in samples] if across else []
+    ab_arg = [dict(abundance, _across=state) for state in carried] if across else rep(abundance)
+    extra = [ab_arg, rep(coverage), rep(pileup)] if abundance or coverage or pileup else []     # the arguments `aligner` does not have
     try:
         for part in indexes_paths[:-1]:
             index = index_loader(part)
@@ -181,6 +187,9 @@ def multi_threaded_aligner(query_folder, indexes_paths, mode=None, mapping_quali
     finally:
         _trace("mapped", 0, time.perf_counter())
         pool.close()
+        for state in carried:
+            if state["carry"] is not None:
+                state["carry"].close()
         _capi.set_io_workers(1)
     t0 = time.perf_counter()
     try:
@@ -208,8 +217,14 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     `abundance` (None / False: off, and nothing changes -- same outputs, same files): True, or a dict with any of
     cap_cands / max_delta / scale_q (`mappy_compat.Aligner.abundance`) and max_iter / tol_q32 (`Abundance.solve`), collects
     every read's candidate genomes from every batch, solves the EM at the end of the sample and leaves
-    `<sample_name>.abundance.csv` (`ABUNDANCE_CSV_HEADER`, one row per genome) beside the routed files.  Only for a
-    database of one index part: with carried hits or a part that is not the last, ValueError before anything runs.
+    `<sample_name>.abundance.csv` (`ABUNDANCE_CSV_HEADER`, one row per genome) beside the routed files.  As it stands only
+    for a database of one index part: with carried hits or a part that is not the last, ValueError before anything runs.
+    With "across_parts": True in the dict, `multi_threaded_aligner` takes a database of several parts: it keeps one
+    candidate carry (`_capi.Carry`, "width" pairs per read, default `_capi.CARRY_WIDTH`) per sample for the length of its
+    call and hands it on in the sample's dict.  Every part's run carries its batches into it -- a read is the row of its
+    ordinal in the file, a part's genomes follow those of the parts before it -- and the last part's run adds the rows to
+    an accumulator for the genomes of all parts, solves, and writes the same file.  A genome name that occurs in two
+    parts is a ValueError.
 
     `coverage` (None / False: off, and nothing changes -- same outputs, same files): True, or the
     bin width in bases, makes a device accumulator for this sample and index part (`mappy_compat.Aligner.coverage`),
@@ -236,8 +251,16 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     if mapping_quality is None:
         raise TypeError("'>=' not supported between instances of 'int' and 'NoneType'")
     carried_file = os.path.join(hits_folder, sample_name + "_hits.pkl")
-    if abundance and (not last_index or os.path.exists(carried_file)):
+    ab_opts = dict(abundance) if isinstance(abundance, dict) else {}
+    ab_across = ab_opts.get("_across")                    # the sample's carry over the parts (`multi_threaded_aligner`), or None
+    if abundance and ab_across is None and (not last_index or os.path.exists(carried_file)):
         raise ValueError(ABUNDANCE_MULTI_PART)
+    if ab_across is not None:
+        part_names = list(index.index.genome_names)
+        seen_names = set(ab_across["names"])
+        for name in part_names:
+            if name in seen_names:
+                raise ValueError(f"genome {name!r} occurs in two index parts: abundance across parts needs every genome in one part")
     sample_hits = _capi.HitMap(carried_file if os.path.exists(carried_file) else None)
     t_engine = time.perf_counter()
     engine = index.engine()
@@ -250,13 +273,25 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
         cov = index.coverage(COVERAGE_BIN_BASES if coverage is True else int(coverage))
         cov_what = _capi.COV_ASSIGNED if last_index and not os.path.exists(carried_file) else _capi.COV_GATED
     pile = index.pileup() if pileup else None
-    ab_opts = dict(abundance) if isinstance(abundance, dict) else {}
-    abund = index.abundance(**{k: v for k, v in ab_opts.items() if k in ("cap_cands", "max_delta", "scale_q")}) if abundance else None
+    ab_args = {k: v for k, v in ab_opts.items() if k in ("cap_cands", "max_delta", "scale_q")}
+    abund = index.abundance(**ab_args) if abundance and ab_across is None else None
+    carry, reads_seen = None, [0]                         # (reads_seen: the file's reads classified so far, in file order)
+    if ab_across is not None:
+        if ab_across["carry"] is None:
+            ab_across["carry"] = index.carry(0, **{k: v for k, v in ab_opts.items() if k in ("width", "max_delta")})
+        carry = ab_across["carry"]
+        genome_offset = len(ab_across["names"])
+
+    def carry_batch(batch):
+        carry.reserve(reads_seen[0] + batch.n)
+        engine.carry_candidates(carry, reads_seen[0], genome_offset)
+
     # what every classified batch is added to (asynchronously, behind the batch's kernels), and what a message calls it
     adds = [(add, noun) for accum, add, noun in (
-        (cov, lambda: engine.add_coverage(cov, cov_what), "coverage"),
-        (pile, lambda: engine.add_pileup(pile, _capi.COV_GATED), "pileup"),
-        (abund, lambda: engine.add_abundance(abund), "abundance candidates")) if accum is not None]
+        (cov, lambda batch: engine.add_coverage(cov, cov_what), "coverage"),
+        (pile, lambda batch: engine.add_pileup(pile, _capi.COV_GATED), "pileup"),
+        (abund, lambda batch: engine.add_abundance(abund), "abundance candidates"),
+        (carry, carry_batch, "abundance candidates")) if accum is not None]
 
     clock = TIMINGS.setdefault(sample_name, dict.fromkeys(("parse", "classify", "carry", "route", "count", "engine", "open", "close", "remove"), 0.0))
     clock["engine"] += t_engine
@@ -362,11 +397,12 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
             out = engine.classify_ptr(batch.bases_ptr, batch.offsets_ptr, batch.n, mapping_quality)
         for add, noun in adds:
             try:
-                add()
+                add(batch)
             except _capi.MncError as err:
                 if err.code != _capi.ERR_UNSUPPORTED:
                     raise
                 print(f"{sample_name}: a batch that mixes reads of 2^20 bases or more with shorter ones adds no {noun}")
+        reads_seen[0] += batch.n
         clock["classify"] += time.perf_counter() - t1
         _trace("classify", batch.n, t1)
         n_skipped = int((out[0] == _capi.SKIPPED).sum())
@@ -520,6 +556,19 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
         write_abundance_csv(abund, os.path.join(mapped_folder, sample_name + ".abundance.csv"),
                             **{k: v for k, v in ab_opts.items() if k in ("max_iter", "tol_q32")})
 
+    if ab_across is not None and not post_error:
+        ab_across["names"].extend(part_names)
+        if last_index:                                    # every part has been carried: the rows go to an accumulator of all genomes
+            abund = index.abundance_global(ab_across["names"], **ab_args)
+            try:
+                abund.add_carry(carry, 0, reads_seen[0])
+                n_truncated = carry.info()["n_truncated_reads"]
+            except BaseException:
+                abund.close()
+                raise
+            if n_truncated:
+                print(f"{sample_name}: {n_truncated} read(s) had more than {carry.width} candidate genomes; the {carry.width} best of each were kept "
+                      f"(abundance width = {carry.width})")
     outputs = [(a, write) for a, write in ((cov, write_coverage), (pile, write_variants), (abund, write_abundance)) if a is not None]
     try:
         for accum, write in outputs:
@@ -569,14 +618,14 @@ def write_coverage_csv(cov, path):
 
 
 def write_abundance_csv(abund, path, **solve_args):
-    """One row per genome of the accumulator's index, written to `path`: the EM's share of the sample (`theta`), the reads
+    """One row per genome of the accumulator (of its index, or of a whole database's parts in order), written to `path`: the EM's share of the sample (`theta`), the reads
     it attributes to the genome and the reads that had no other candidate.  The floats are written with `repr`, so they
     read back as the doubles `Abundance.solve` returned."""
     theta, expected, _ = abund.solve(**solve_args)
     unique = abund.unique()
     with open(path, "w") as out:
         out.write(",".join(ABUNDANCE_CSV_HEADER) + "\n")
-        for g, name in enumerate(abund.index.genome_names):
+        for g, name in enumerate(abund.genome_names):
             out.write("{},{!r},{!r},{}\n".format(name, float(theta[g]), float(expected[g]), int(unique[g])))
 
 

@@ -32,6 +32,7 @@ struct Accum {
 	hipStream_t st = nullptr;
 	hipEvent_t ev_add = nullptr, ev_own = nullptr;
 	std::vector<void*> bufs;                   // the device allocations, as `alloc` made them
+	bool serial = false;                       // adds run one behind the other on the device: each waits for the last one's event
 
 	// ---- creation: begin, alloc per buffer, streams.  `he`, the creating function's own, keeps the first failure and every
 	// step behind it is skipped; release() undoes whatever was made
@@ -75,6 +76,7 @@ struct Accum {
 	{
 		std::lock_guard<std::mutex> lk(mu);
 		HIP_TRY(hipStreamWaitEvent(on, ev_own, 0));             // behind the last reset
+		if (serial) HIP_TRY(hipStreamWaitEvent(on, ev_add, 0)); // ... and behind the last add, whichever engine's it was
 		launch();
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipEventRecord(ev_add, on));

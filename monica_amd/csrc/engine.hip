@@ -104,6 +104,9 @@ const Accum *as_accum(const mnc_abundance *ab);
 int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream_t st);
 int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st);
 int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st);
+// the candidate carry (k_carry.hip): an Accum of a device, of no index
+const Accum *as_accum(const mnc_carry *cc);
+int carry_add(mnc_carry *cc, const Batch &B, int n_contigs, int n_genomes, int64_t first_read, int32_t genome_offset, hipStream_t st);
 
 // ---------------------------------------------------------------- run offsets of the partition
 // The sketch writes one histogram row per tile ([tile][bucket]); the query records are laid out
@@ -1741,10 +1744,11 @@ static int add_selector(int what, bool pileup, int *sel)
 
 // What every add checks, beside its selector, before it touches anything.  noun: what the call adds, for the wide-pass
 // refusal.  need_dp: the message when the batch's contract is not MNC_CONTRACT_DP; nullptr where any contract serves.
-static int add_precheck(const mnc_engine *e, const Accum *a, const char *noun, const char *need_dp)
+// any_index: an accumulator of a device alone (the candidate carry), which serves whatever index the engine holds.
+static int add_precheck(const mnc_engine *e, const Accum *a, const char *noun, const char *need_dp, bool any_index = false)
 {
 	if (!e || !a) return MNC_ERR_ARG;
-	if (a->idx != e->idx || a->device != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
+	if ((!any_index && a->idx != e->idx) || a->device != e->device) { set_error("the accumulator belongs to another index or device than the engine's"); return MNC_ERR_ARG; }
 	if (!e->have_batch) { set_error("no batch has been classified"); return MNC_ERR_ARG; }
 	if (e->have_merged) {
 		set_error("the last call ran both the usual and the wide pass (reads of 2^20 bases or more among shorter ones): the engine holds the wide pass "
@@ -1788,6 +1792,21 @@ extern "C" int mnc_engine_add_abundance(mnc_engine *e, mnc_abundance *ab)
 	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
 	return abundance_add(ab, e->B, e->stream);
+}
+
+// ---------------------------------------------------------------- candidates of the last batch, carried across index parts
+// The same records once more, merged into the rows of a candidate carry (k_carry.hip): read r of the batch is read
+// first_read + r of the sample, genome g of the engine's index is genome_offset + g of the database.
+extern "C" int mnc_engine_carry_candidates(mnc_engine *e, mnc_carry *cc, int64_t first_read, int32_t genome_offset)
+{
+	if (!e || !cc) return MNC_ERR_ARG;
+	if (first_read < 0 || genome_offset < 0) { set_error("first_read %lld, genome_offset %d: neither may be negative", (long long)first_read, genome_offset); return MNC_ERR_ARG; }
+	if (int rc = add_precheck(e, as_accum(cc), "candidates", "carried candidates need the dp_max of MNC_CONTRACT_DP", true)) return rc;
+	const int64_t n_genomes = (int64_t)e->idx->genome_name.size();
+	if ((int64_t)genome_offset + n_genomes - 1 > INT32_MAX) { set_error("genome_offset %d + %lld genomes: a global genome id is an int32", genome_offset, (long long)n_genomes); return MNC_ERR_ARG; }
+	if (e->B.n_reads == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return carry_add(cc, e->B, (int)e->idx->contig_len.size(), (int)n_genomes, first_read, genome_offset, e->stream);
 }
 
 // ---------------------------------------------------------------- counters / dumps

@@ -15,6 +15,9 @@
 //                    slots) by a compare-and-swap loop of lane 0, so row r starts where row r - 1 ends -- offsets is a true
 //                    CSR whatever order the waves arrive in -- and a row that does not fit takes nothing: it is counted in
 //                    n_dropped and the word stays as it was.  No host wait.
+//   mnc_ab_collect_carry  the same treatment for the rows of a candidate carry (k_carry.hip; mnc_abundance_add_carry, for a
+//                    database of several index parts): one wave per row, a pair per lane, ascending genome id by rank, the
+//                    same reservation.
 //   mnc_ab_pass      one EM iteration's E and M step in one pass over the CSR, one thread per ROW (rows hold 2-6 pairs: 8
 //                    bytes per candidate, 8 per row offset, and the theta gathers).  Every product, sum and quotient is one
 //                    IEEE double operation rounded to nearest (__dmul_rn / __dadd_rn / __ddiv_rn; no fused multiply-add);
@@ -34,13 +37,7 @@
 #include <algorithm>
 #include <new>
 #include <vector>
-#include "device.h"
-#pragma clang diagnostic push                  // (the header's scan kernels are for the two accumulators over the reference bases)
-#pragma clang diagnostic ignored "-Wunused-function"
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#include "cov_common.h"
-#pragma clang diagnostic pop
-#include "accum.h"
+#include "ab_common.h"                         // (the records that count and the extraction rounds: shared with k_carry.hip)
 
 using namespace mnc;
 
@@ -71,33 +68,23 @@ struct mnc_abundance : Accum {                 // (ev_own: the last reset or add
 namespace mnc {
 
 // ---------------------------------------------------------------- collect
-__device__ __forceinline__ unsigned long long ab_wave_min(unsigned long long x)
-{
-	for (int d = 32; d > 0; d >>= 1) {
-		const unsigned long long o = __shfl_xor(x, d);
-		x = o < x ? o : x;
-	}
-	return x;
-}
+// (ab_best, ab_next and the key they share: ab_common.h)
 
-// the key of one record: genome in the high word, the score inverted in the low one (order-preserving for any int32), so
-// that the minimum is the smallest genome and within it the largest score
-__device__ __forceinline__ unsigned long long ab_key(int g, int s) { return (unsigned long long)(uint32_t)g << 32 | (uint32_t)~((uint32_t)s ^ 0x80000000u); }
-__device__ __forceinline__ int ab_key_score(unsigned long long k) { return (int)(~(uint32_t)k ^ 0x80000000u); }
-
-// the smallest key above genome `last` among the read's records that count; ~0 when there is none
-__device__ __forceinline__ unsigned long long ab_next(const Batch &B, int64_t slot0, int n, int n_contigs, int n_genomes, int last)
+// Lane 0 of a wave reserves one row and its k candidate slots together, or drops the row: the word as it stood before the
+// reservation (rows << 33 | slots: the row's number and its first slot), ~0 for a row that does not fit.  Counted in
+// n_reads or in n_dropped either way.
+__device__ __forceinline__ unsigned long long ab_reserve(unsigned long long *ctr, int k, int64_t cap_cands, int64_t cap_rows)
 {
-	unsigned long long k = ~0ull;
-	for (int i = lane_id(); i < n; i += 64) {
-		const mnc_reg_t &r = B.regs[slot0 + i];
-		if (!cov_selected(r, MNC_COV_ALL, B.min_mapq) || r.rid < 0 || r.rid >= n_contigs || r.n_cigar <= 0) continue;
-		const int g = B.contig_genome[r.rid];
-		if (g <= last || g >= n_genomes) continue;
-		const unsigned long long x = ab_key(g, r.dp_max);
-		k = x < k ? x : k;
+	unsigned long long got = ~0ull;
+	unsigned long long cur = __hip_atomic_load(ctr + ABC_PACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	for (;;) {
+		const int64_t rows = (int64_t)(cur >> AB_SLOT_BITS), slots = (int64_t)(cur & AB_SLOT_MASK);
+		if (slots + k > cap_cands || rows + 1 > cap_rows) break;
+		const unsigned long long want = cur + (1ull << AB_SLOT_BITS) + (unsigned long long)k;
+		if (__hip_atomic_compare_exchange_strong(ctr + ABC_PACK, &cur, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { got = cur; break; }
 	}
-	return ab_wave_min(k);
+	(void)__hip_atomic_fetch_add(ctr + (got == ~0ull ? ABC_DROPPED : ABC_READS), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	return got;
 }
 
 __global__ __launch_bounds__(256) void mnc_ab_collect(Batch B, int n_contigs, int n_genomes, int max_delta, int64_t cap_cands, int64_t cap_rows,
@@ -110,20 +97,8 @@ __global__ __launch_bounds__(256) void mnc_ab_collect(Batch B, int n_contigs, in
 	if (n <= 0) return;
 	const int64_t slot0 = reg_slot(B, rd);
 	// ---- best: the largest dp_max of the records that count
-	bool any = false;
-	int best = INT32_MIN;
-	for (int i = lane; i < n; i += 64) {
-		const mnc_reg_t &r = B.regs[slot0 + i];
-		if (!cov_selected(r, MNC_COV_ALL, B.min_mapq) || r.rid < 0 || r.rid >= n_contigs || r.n_cigar <= 0) continue;
-		const int g = B.contig_genome[r.rid];
-		if (g < 0 || g >= n_genomes) continue;
-		any = true, best = r.dp_max > best ? r.dp_max : best;
-	}
-	if (!__ballot(any)) return;                               // a read with no record adds nothing
-	for (int d = 32; d > 0; d >>= 1) {
-		const int o = __shfl_xor(best, d);
-		best = o > best ? o : best;
-	}
+	int best;
+	if (!ab_best(B, slot0, n, n_contigs, n_genomes, best)) return;   // a read with no record adds nothing
 	// ---- count the candidates
 	int k = 0, only = -1;
 	for (int last = -1;;) {
@@ -141,16 +116,7 @@ __global__ __launch_bounds__(256) void mnc_ab_collect(Batch B, int n_contigs, in
 	}
 	// ---- reserve row and slots together, or drop the row
 	unsigned long long got = ~0ull;
-	if (lane == 0) {
-		unsigned long long cur = __hip_atomic_load(ctr + ABC_PACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		for (;;) {
-			const int64_t rows = (int64_t)(cur >> AB_SLOT_BITS), slots = (int64_t)(cur & AB_SLOT_MASK);
-			if (slots + k > cap_cands || rows + 1 > cap_rows) break;
-			const unsigned long long want = cur + (1ull << AB_SLOT_BITS) + (unsigned long long)k;
-			if (__hip_atomic_compare_exchange_strong(ctr + ABC_PACK, &cur, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { got = cur; break; }
-		}
-		(void)__hip_atomic_fetch_add(ctr + (got == ~0ull ? ABC_DROPPED : ABC_READS), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
+	if (lane == 0) got = ab_reserve(ctr, k, cap_cands, cap_rows);
 	got = __shfl(got, 0);
 	if (got == ~0ull) return;
 	const int64_t row = (int64_t)(got >> AB_SLOT_BITS), start = (int64_t)(got & AB_SLOT_MASK);
@@ -166,6 +132,43 @@ __global__ __launch_bounds__(256) void mnc_ab_collect(Batch B, int n_contigs, in
 		++j;
 	}
 	if (lane == 0) offsets[row] = start, offsets[row + 1] = start + k;   // (row r + 1 writes the same value into its own first word)
+}
+
+// A carry's rows [first, first + n) (k_carry.hip), each treated as mnc_ab_collect treats a read: one wave per row, the
+// row's pairs one per lane.  Ascending genome id by rank: a pair's place is the number of the row's pairs with a smaller id.
+// The host has checked that the carry holds no id >= n_genomes.
+__global__ __launch_bounds__(256) void mnc_ab_collect_carry(const int2 *head, const int2 *slots, int width, int64_t first, int64_t n, int n_genomes,
+                                                            int64_t cap_cands, int64_t cap_rows, int64_t *unique, int64_t *offsets, int32_t *genome,
+                                                            int32_t *delta, unsigned long long *ctr)
+{
+	const int lane = lane_id();
+	const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	if (r >= n) return;                                       // (whole waves; no workgroup barrier)
+	const int2 h = head[first + r];
+	if (!(h.y & CARRY_USED)) return;
+	const int2 p = lane < width ? slots[(first + r) * width + lane] : make_int2(-1, 0);
+	const bool valid = p.x >= 0 && p.x < n_genomes;
+	const int k = __popcll(__ballot(valid));
+	if (k == 0) return;
+	if (k == 1) {
+		if (valid) {
+			(void)__hip_atomic_fetch_add(unique + p.x, (int64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			(void)__hip_atomic_fetch_add(ctr + ABC_READS, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+		return;
+	}
+	int rank = 0;
+	for (int i = 0; i < width; ++i) {
+		const int gi = __shfl(p.x, i);
+		rank += gi >= 0 && gi < p.x;
+	}
+	unsigned long long got = ~0ull;
+	if (lane == 0) got = ab_reserve(ctr, k, cap_cands, cap_rows);
+	got = __shfl(got, 0);
+	if (got == ~0ull) return;
+	const int64_t row = (int64_t)(got >> AB_SLOT_BITS), start = (int64_t)(got & AB_SLOT_MASK);
+	if (valid) genome[start + rank] = p.x, delta[start + rank] = (int32_t)((long long)h.x - p.y);   // (rank < k: start + k <= cap_cands)
+	if (lane == 0) offsets[row] = start, offsets[row + 1] = start + k;
 }
 
 // ---------------------------------------------------------------- solve
@@ -304,9 +307,9 @@ extern "C" void mnc_abundance_free(mnc_abundance *ab)
 	delete ab;
 }
 
-extern "C" int mnc_abundance_create(mnc_index *idx, int device, int64_t cap_cands, int32_t max_delta, int32_t scale_q, mnc_abundance **out)
+// for the genomes of `idx`, or -- idx = NULL -- for n_genomes genomes of no index (mnc_abundance_create_global)
+static int ab_create(mnc_index *idx, int32_t n_genomes, int device, int64_t cap_cands, int32_t max_delta, int32_t scale_q, mnc_abundance **out)
 {
-	if (!idx || !out) return MNC_ERR_ARG;
 	*out = nullptr;
 	if (cap_cands < 0 || cap_cands >= AB_MAX_CANDS) { set_error("cap_cands %lld outside 0 .. 2^32 - 1", (long long)cap_cands); return MNC_ERR_ARG; }
 	if (max_delta < 0 || scale_q < 1 || (int64_t)max_delta * scale_q > 4000) {
@@ -316,7 +319,7 @@ extern "C" int mnc_abundance_create(mnc_index *idx, int device, int64_t cap_cand
 	if (int rc = check_device(device)) return rc;
 	mnc_abundance *ab = new (std::nothrow) mnc_abundance;
 	if (!ab) return MNC_ERR_NOMEM;
-	ab->n_contigs = (int)idx->contig_len.size(), ab->G = (int)idx->genome_name.size();
+	ab->n_contigs = idx ? (int)idx->contig_len.size() : 0, ab->G = idx ? (int)idx->genome_name.size() : (int)n_genomes;
 	ab->cap_cands = cap_cands, ab->cap_rows = cap_cands / 2, ab->max_delta = max_delta, ab->scale_q = scale_q;
 	const size_t G = (size_t)ab->G;
 	hipError_t he = ab->begin(idx, device);
@@ -338,6 +341,46 @@ extern "C" int mnc_abundance_create(mnc_index *idx, int device, int64_t cap_cand
 	if (int rc = mnc_abundance_reset(ab)) { mnc_abundance_free(ab); return rc; }
 	*out = ab;
 	return MNC_OK;
+}
+
+extern "C" int mnc_abundance_create(mnc_index *idx, int device, int64_t cap_cands, int32_t max_delta, int32_t scale_q, mnc_abundance **out)
+{
+	if (!idx || !out) return MNC_ERR_ARG;
+	return ab_create(idx, 0, device, cap_cands, max_delta, scale_q, out);
+}
+
+extern "C" int mnc_abundance_create_global(int device, int32_t n_genomes, int64_t cap_cands, int32_t max_delta, int32_t scale_q, mnc_abundance **out)
+{
+	if (!out) return MNC_ERR_ARG;
+	*out = nullptr;
+	if (n_genomes < 0) { set_error("n_genomes %d: a number of genomes", n_genomes); return MNC_ERR_ARG; }
+	return ab_create(nullptr, n_genomes, device, cap_cands, max_delta, scale_q, out);
+}
+
+// The rows [first_read, first_read + n_reads) of a carry, each as one read.  The one wait is for the carry's largest genome
+// id (every check comes before anything is added); the add itself is queued on the accumulator's stream.
+extern "C" int mnc_abundance_add_carry(mnc_abundance *ab, mnc_carry *cc, int64_t first_read, int64_t n_reads)
+{
+	if (!ab || !cc) return MNC_ERR_ARG;
+	if (first_read < 0 || n_reads < 0) { set_error("rows [%lld, + %lld): a range of reads", (long long)first_read, (long long)n_reads); return MNC_ERR_ARG; }
+	if (cc->device != ab->device) { set_error("the carry is on device %d, the accumulator on device %d", cc->device, ab->device); return MNC_ERR_ARG; }
+	if (cc->max_delta != ab->max_delta) { set_error("the carry was cut at max_delta %d, the accumulator's is %d", cc->max_delta, ab->max_delta); return MNC_ERR_ARG; }
+	if (n_reads > cc->cap || first_read > cc->cap - n_reads) {
+		set_error("rows [%lld, %lld) of a carry of %lld", (long long)first_read, (long long)(first_read + n_reads), (long long)cc->cap);
+		return MNC_ERR_RANGE;
+	}
+	unsigned long long s[4];
+	if (int rc = carry_stats(cc, s)) return rc;
+	if ((int64_t)s[3] > ab->G) { set_error("the carry holds genome id %lld, the accumulator has %d genomes", (long long)s[3] - 1, ab->G); return MNC_ERR_ARG; }
+	if (n_reads == 0 || ab->G == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(ab->device));
+	std::lock_guard<std::mutex> lk(ab->mu);
+	if (int rc = carry_read_begin(cc, ab->st)) return rc;
+	hipLaunchKernelGGL(mnc_ab_collect_carry, dim3((unsigned)((n_reads + 3) / 4)), dim3(256), 0, ab->st, cc->head, cc->slots, (int)cc->width, first_read, n_reads, ab->G,
+	                   ab->cap_cands, ab->cap_rows, ab->unique, ab->offsets, ab->genome, ab->delta, ab->ctr);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(ab->own_done());                                   // an engine's add, and whatever changes the carry, comes behind it
+	return carry_read_end(cc, ab->ev_own);
 }
 
 extern "C" int mnc_abundance_reset(mnc_abundance *ab)

@@ -341,6 +341,15 @@ class Aligner:
         then `solve()` it."""
         return _capi.Abundance(self._index, self._device, cap_cands, max_delta, scale_q)
 
+    def carry(self, cap_reads=0, width=_capi.CARRY_WIDTH, max_delta=_capi.ABUNDANCE_MAX_DELTA):
+        """A candidate carry (`_capi.Carry`) on this object's device, for a database of several index parts: every part's
+        engine carries its batches into it (`Engine.carry_candidates`), and `abundance_global` takes it at the end."""
+        return _capi.Carry(self._device, cap_reads, width, max_delta)
+
+    def abundance_global(self, genome_names, cap_cands=_capi.ABUNDANCE_CAP_CANDS, max_delta=_capi.ABUNDANCE_MAX_DELTA, scale_q=_capi.ABUNDANCE_SCALE_Q):
+        """An abundance accumulator for the genomes of a whole database (`_capi.Abundance.global_`) on this object's device."""
+        return _capi.Abundance.global_(self._device, len(genome_names), cap_cands, max_delta, scale_q, genome_names=genome_names)
+
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
                   abundance=None):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
