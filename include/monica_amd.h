@@ -185,8 +185,17 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   pileup after a call that ran both the usual  mnc_engine_add_pileup: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
  *   and the wide pass                            coverage); a call whose reads are all long adds like any other
  *   pileup under MNC_CONTRACT_CHAIN              mnc_engine_add_pileup: MNC_ERR_ARG (no CIGAR to take the columns from)
- *   the bases of an insertion                    inserted bases are not stored: mnc_pileup counts an insertion once, at the
- *                                                reference base on its left, whatever it inserts
+ *   the bases of an insertion                    stored when mnc_pileup_store_insertions was called (insertion alleles, below).
+ *                                                Without that call the inserted bases are not stored: mnc_pileup counts an
+ *                                                insertion once, at the reference base on its left, whatever it inserts
+ *   more than cap_alleles different insertion    once the table is seen to hold cap_alleles (a count kept per record added, so
+ *   alleles, or 128 taken slots in a row (the    with the lag of the records in flight: not a hard bound) or within the probe
+ *   probe limit)                                 limit the event finds no slot and is counted in n_dropped;
+ *                                                mnc_pileup_call_insertions and mnc_pileup_consensus_ins: MNC_ERR_RANGE until
+ *                                                mnc_pileup_reset.  The eight planes are not affected
+ *   long alleles beyond cap_pool_bases           the allele keeps its exact count without bases and is counted in
+ *                                                n_pool_dropped; the same two read-outs: MNC_ERR_RANGE until mnc_pileup_reset
+ *   cap_alleles above 2^30                       mnc_pileup_store_insertions: MNC_ERR_ARG
  *   a reference base with 2^31 or more           outside the contract: every plane of mnc_pileup holds int32 per base
  *   observations in one pileup plane             (mnc_pileup_reset starts over)
  *   abundance after a call that ran both the     mnc_engine_add_abundance: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
@@ -503,7 +512,8 @@ int  mnc_coverage_device(mnc_coverage *cov, const int32_t **d_track, int64_t *n_
  *   I operation                                  ins[q] += 1 ONCE per operation, whatever its length: q is the reference
  *                                                position of the last reference-consuming column before it in that record.
  *                                                An I with no such column is not counted (mm_fix_cigar leaves none).
- *                                                THE INSERTED BASES ARE NOT STORED: an insertion is known by place and count
+ *                                                The inserted bases are stored when mnc_pileup_store_insertions was called
+ *                                                (insertion alleles, below); otherwise an insertion is known by place and count
  * The result is eight planes per reference base, in this order: depth, A, C, G, T, N, DEL, INS (MNC_PILE_*), all exact
  * integers.  Addition commutes: the result does not depend on order or on how a sample was cut into batches.
  * Derived: span[p] = depth[p] + del[p], the records that say something about base p.
@@ -536,7 +546,7 @@ typedef struct {
 	int32_t span;                /* depth + del at pos */
 	int32_t count;               /* observations of `alt` at pos */
 	uint8_t ref;                 /* 'A' 'C' 'G' 'T' */
-	uint8_t alt;                 /* 'A' 'C' 'G' 'T', '-' (deleted), '+' (an insertion follows; its bases are not stored) */
+	uint8_t alt;                 /* 'A' 'C' 'G' 'T', '-' (deleted), '+' (an insertion follows; what it inserts: mnc_pileup_call_insertions) */
 	uint8_t pad[2];              /* 0 */
 } mnc_variant_t;
 /* MNC_ERR_NODEVICE without a gfx950 device, MNC_ERR_ARG for an index without contig bases, MNC_ERR_NOMEM when the 32 bytes
@@ -544,9 +554,10 @@ typedef struct {
 int  mnc_pileup_create(mnc_index *idx, int device, mnc_pileup **out);
 /* frees the accumulator and the HBM it holds (waits for the work queued on it) */
 void mnc_pileup_free(mnc_pileup *pu);
-/* clears every plane; asynchronous */
+/* clears every plane, and the insertion store if there is one; asynchronous */
 int  mnc_pileup_reset(mnc_pileup *pu);
-/* HBM the accumulator holds: 32 bytes per reference base, a few words per contig and 24 bytes per 1 024 bases of scratch */
+/* HBM the accumulator holds: 32 bytes per reference base, a few words per contig and 24 bytes per 1 024 bases of scratch;
+ * with mnc_pileup_store_insertions 40 bytes per slot and the pool besides */
 int  mnc_pileup_device_bytes(const mnc_pileup *pu, int64_t *bytes);
 /* The raw additive planes (device pointers), laid out as above; either pointer may be NULL.  Ordered behind the adds only
  * after a read-out call below or a sync of the engines that added. */
@@ -570,9 +581,64 @@ int  mnc_pileup_call_variants(mnc_pileup *pu, int rid, int32_t min_depth, int32_
                               mnc_variant_t *out, int64_t cap, int64_t *n);
 /* One character per base of [start, end) of contig rid (not NUL-terminated; the interval checked as above): 'N' where
  * span < min_depth; otherwise the largest of the counts of A, C, G, T and DEL -- on a tie the reference base if it is
- * among the tied, else the first of them in that order -- written 'A' 'C' 'G' 'T' or '-'.  Insertions do not appear:
- * their bases are not stored. */
+ * among the tied, else the first of them in that order -- written 'A' 'C' 'G' 'T' or '-'.  Insertions do not appear
+ * here; mnc_pileup_consensus_ins writes them, where they are stored. */
 int  mnc_pileup_consensus(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t min_depth, char *out /* end - start */);
+
+/* ---- insertion alleles (opt-in per accumulator)
+ * mnc_pileup_store_insertions gives the accumulator a device hash table of insertion ALLELES: what was inserted, not only
+ * that something was.  An allele is (place, length, bases): the place is the contig and pos, the reference base on the
+ * insertion's left -- exactly where the INS plane counts it; the bases are the inserted bases on the hit's strand as codes
+ * A C G T N (the query columns of the I operation as defined above: for rev = 1 the complement of the reversed read; case
+ * folded, U as T, anything else N).  An I that the INS plane does not count (no reference column on its left in its record,
+ * length 0, a place outside the contig) is not stored either, so with nothing dropped the counts of all alleles at a place
+ * sum to ins[place] -- for what the engines added; mnc_pileup_add_insertion_list does NOT touch the INS plane.
+ * Called at most once, before the first add: a call after an add, a second call, cap_alleles <= 0 (or > 2^30) or
+ * cap_pool_bases < 0 is MNC_ERR_ARG.  The table has the next power of two of slots that keeps the load at 0.5 or below
+ * (40 bytes a slot); alleles of up to 32 bases without an N are packed into their slot, longer ones and those with an N take
+ * ceil(len / 2) bytes of a pool of cap_pool_bases / 2 bytes.  mnc_pileup_reset clears both, mnc_pileup_device_bytes includes
+ * both.  A pileup that never calls it runs the same add kernel as ever and allocates nothing.
+ * Adding never waits: a slot is claimed by one compare-and-swap on a 64-bit fingerprint of the allele, the count is one
+ * atomic add.  Beside the count a slot keeps the wrapping sum of a second, independent 64-bit hash of every event; the
+ * read-outs check sum == count * h2(stored allele) and count the slots that fail in n_collisions: two alleles of one
+ * fingerprint are detected (up to a 2^-128 event), not merged in silence.
+ * Overflow: an event that finds no slot within 128 probes, or a new allele while the table holds cap_alleles, is counted in
+ * n_dropped; an allele whose bases do not fit the pool keeps its exact count, has no bases and is counted in n_pool_dropped.
+ * (The add kernels count their claims once per record, so cap_alleles takes hold with the lag of the records in flight; the
+ * slots, twice cap_alleles or more, and the probe limit bound what that lag can add, and n_alleles is what is there.)
+ * Which event is dropped depends on the order of arrival, so while n_dropped, n_pool_dropped or n_collisions is not 0,
+ * mnc_pileup_call_insertions and mnc_pileup_consensus_ins return MNC_ERR_RANGE and write nothing (the rule
+ * mnc_abundance_solve keeps for its n_dropped).  The eight planes are never affected. */
+int  mnc_pileup_store_insertions(mnc_pileup *pu, int64_t cap_alleles, int64_t cap_pool_bases);
+/* Adds n alleles made by the caller -- typically a rank that has gathered what the other ranks fetched with
+ * mnc_pileup_call_insertions -- on the accumulator's own stream, through the insert path of the engine's adds: row i is
+ * count[i] observations of the len[i] bases at bases + base_off[i] (ASCII, on the hit's strand) behind base pos[i] of contig
+ * rid[i].  Only the store is added to: no plane, the INS plane included.  MNC_ERR_ARG, the accumulator untouched: no store;
+ * a rid out of range, a pos outside its contig, len <= 0, count <= 0, or base offsets that do not ascend (base_off[i] >=
+ * base_off[i - 1] + len[i - 1], base_off[0] >= 0).  Returns when the host arrays have been read.  Like reset and the
+ * read-outs it is for one thread at a time, but engines may be adding from their own threads meanwhile: the rows go through
+ * the same claims, and an engine's add queued after this call returns comes behind it. */
+int  mnc_pileup_add_insertion_list(mnc_pileup *pu, int64_t n, const int32_t *rid, const int32_t *pos, const int32_t *len, const int32_t *count,
+                                   const int64_t *base_off, const uint8_t *bases /* ASCII */);
+/* The totals (any pointer may be NULL): alleles held and the events counted in them, events dropped, pool places taken
+ * (two per byte) and alleles without bases, slots that fail the collision check.  MNC_ERR_ARG without a store. */
+int  mnc_pileup_insertion_info(mnc_pileup *pu, int64_t *n_alleles, int64_t *n_events, int64_t *n_dropped, int64_t *n_pool_bases, int64_t *n_pool_dropped,
+                               int64_t *n_collisions);
+/* one called insertion allele (mnc_pileup_call_insertions): 32 bytes */
+typedef struct { int32_t rid, pos, span, count, len; int32_t pad; int64_t base_off; } mnc_insertion_t;
+/* The insertion alleles of contig rid, or of every contig for rid = -1, by the rule of mnc_pileup_call_variants applied per
+ * allele: called iff the reference base at pos is not N, span >= min_depth, count >= min_count and count * 1000 >=
+ * min_permille * span (int64), span = depth + del at pos.  (0, 1, 0) fetches everything.  The records are in ascending
+ * (rid, pos, len, bases) order, bases compared as codes A < C < G < T < N -- an order made on the device that owes nothing
+ * to the table or to the order of the adds; record k's bases are upper-case ASCII at bases + base_off, in record order
+ * without gaps.  *n and *n_bases are always set; MNC_ERR_RANGE with nothing written when cap or cap_bases is short. */
+int  mnc_pileup_call_insertions(mnc_pileup *pu, int rid, int32_t min_depth, int32_t min_count, int32_t min_permille,
+                                mnc_insertion_t *out, int64_t cap, int64_t *n, char *bases, int64_t cap_bases, int64_t *n_bases);
+/* mnc_pileup_consensus with the insertions: for every base of [start, end) the character mnc_pileup_consensus writes
+ * ('-' and 'N' included) and, behind it, in LOWER case, the bases of the insertion allele with the largest count at that base
+ * (a tie: the first in the order above) iff span >= min_depth and 2 * count > span.  With its lower-case characters removed
+ * the output is mnc_pileup_consensus of the interval.  *n = the characters; MNC_ERR_RANGE with *n set when cap is short. */
+int  mnc_pileup_consensus_ins(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t min_depth, char *out, int64_t cap, int64_t *n);
 
 /* ---------------------------------------------------------------- abundance
  * Which of several close genomes is in the sample, and how much of each: the other half of the focus pass' question.  The

@@ -46,6 +46,9 @@ COV_SUMMARY_DTYPE = np.dtype([("covered", "<i8"), ("depth_sum", "<i8"), ("max_de
 PILE_PLANES = ("depth", "A", "C", "G", "T", "N", "DEL", "INS")
 VARIANT_DTYPE = np.dtype([("rid", "<i4"), ("pos", "<i4"), ("span", "<i4"), ("count", "<i4"), ("ref", "S1"), ("alt", "S1"), ("pad", "<u2")])
 assert VARIANT_DTYPE.itemsize == 20
+# one row of Pileup.insertions() (mnc_insertion_t, 32 bytes)
+INSERTION_DTYPE = np.dtype([("rid", "<i4"), ("pos", "<i4"), ("span", "<i4"), ("count", "<i4"), ("len", "<i4"), ("pad", "<i4"), ("base_off", "<i8")])
+assert INSERTION_DTYPE.itemsize == 32
 MZ_DTYPE = np.dtype([("hash", "<u4"), ("pos_strand", "<u4")])
 ANCHOR_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8")])
 
@@ -86,6 +89,7 @@ EXPORTS = [
     "mnc_coverage_summary", "mnc_coverage_fetch_bins", "mnc_coverage_fetch_depth", "mnc_coverage_device",
     "mnc_pileup_create", "mnc_pileup_free", "mnc_pileup_reset", "mnc_pileup_device_bytes", "mnc_pileup_device", "mnc_engine_add_pileup",
     "mnc_pileup_fetch_counts", "mnc_pileup_call_variants", "mnc_pileup_consensus",
+    "mnc_pileup_store_insertions", "mnc_pileup_add_insertion_list", "mnc_pileup_insertion_info", "mnc_pileup_call_insertions", "mnc_pileup_consensus_ins",
     "mnc_abundance_create", "mnc_abundance_free", "mnc_abundance_reset", "mnc_abundance_device_bytes", "mnc_engine_add_abundance",
     "mnc_abundance_add_lists", "mnc_abundance_info", "mnc_abundance_fetch_unique", "mnc_abundance_fetch_lists", "mnc_abundance_solve",
     "mnc_abundance_device", "mnc_abundance_create_global", "mnc_abundance_add_carry",
@@ -240,6 +244,11 @@ def lib():
     sig("mnc_pileup_fetch_counts", i32, [vp, i32, i64, i64, vp])
     sig("mnc_pileup_call_variants", i32, [vp, i32, i32, i32, i32, vp, i64, C.POINTER(i64)])
     sig("mnc_pileup_consensus", i32, [vp, i32, i64, i64, i32, vp])
+    sig("mnc_pileup_store_insertions", i32, [vp, i64, i64])
+    sig("mnc_pileup_add_insertion_list", i32, [vp, i64, vp, vp, vp, vp, vp, vp])
+    sig("mnc_pileup_insertion_info", i32, [vp] + [C.POINTER(i64)] * 6)
+    sig("mnc_pileup_call_insertions", i32, [vp, i32, i32, i32, i32, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)])
+    sig("mnc_pileup_consensus_ins", i32, [vp, i32, i64, i64, i32, vp, i64, C.POINTER(i64)])
     sig("mnc_abundance_create", i32, [vp, i32, i64, C.c_int32, C.c_int32, pp])
     sig("mnc_abundance_free", None, [vp])
     sig("mnc_abundance_reset", i32, [vp])
@@ -762,14 +771,22 @@ class Coverage(_Accumulator):
 class Pileup(_Accumulator):
     """Owner of an ``mnc_pileup``: what the reads say at every reference base of one index on one device -- depth, the
     counts of A C G T N, deletions and insertions -- accumulated from batch to batch by `Engine.add_pileup`
-    (include/monica_amd.h, "pileup")."""
+    (include/monica_amd.h, "pileup").  `insertions=(cap_alleles, cap_pool_bases)` makes it store the inserted bases too
+    (`mnc_pileup_store_insertions`): `insertions()`, `insertion_info()`, `add_insertions()`, `consensus(insertions=True)`."""
 
     _c = "pileup"
 
-    def __init__(self, index, device=0):
+    def __init__(self, index, device=0, insertions=None):
         self.index = index
         self._device = device                                   # (`device` is the method below)
         self._create(index, device)
+        if insertions is not None:
+            cap_alleles, cap_pool_bases = insertions
+            try:
+                check(lib().mnc_pileup_store_insertions(self._h, int(cap_alleles), int(cap_pool_bases)))
+            except BaseException:
+                self.close()
+                raise
 
     def _end(self, rid, end):
         return (self.index.contig_lens[rid] if 0 <= rid < len(self.index.contig_lens) else 0) if end is None else int(end)
@@ -793,9 +810,55 @@ class Pileup(_Accumulator):
             check(lib().mnc_pileup_call_variants(self._h, *args, out.ctypes.data, len(out), C.byref(n)))
         return out[:n.value]
 
-    def consensus(self, rid, start=0, end=None, min_depth=1):
-        """One byte per base of [start, end) of contig `rid`: A C G T, '-' (deleted) or N (span < min_depth)."""
+    def insertion_info(self):
+        """`mnc_pileup_insertion_info` as a dict: n_alleles, n_events, n_dropped, n_pool_bases, n_pool_dropped, n_collisions."""
+        names = ("n_alleles", "n_events", "n_dropped", "n_pool_bases", "n_pool_dropped", "n_collisions")
+        v = [C.c_int64(0) for _ in names]
+        check(lib().mnc_pileup_insertion_info(self._h, *(C.byref(x) for x in v)))
+        return {k: int(x.value) for k, x in zip(names, v)}
+
+    def insertions(self, rid=-1, min_depth=0, min_count=1, min_permille=0):
+        """The called insertion alleles of contig `rid`, or of every contig for -1: (records (INSERTION_DTYPE) in
+        (rid, pos, len, bases) order, the list of their bases as `bytes`).  The defaults fetch every allele."""
+        n, nb = C.c_int64(0), C.c_int64(0)
+        args = (int(rid), int(min_depth), int(min_count), int(min_permille))
+        rc = lib().mnc_pileup_call_insertions(self._h, *args, None, 0, C.byref(n), None, 0, C.byref(nb))
+        if rc not in (OK, ERR_RANGE) or (rc == ERR_RANGE and not n.value):     # (ERR_RANGE with nothing to fetch: dropped events)
+            check(rc)
+        out = np.zeros(n.value, dtype=INSERTION_DTYPE)
+        bases = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        if len(out):
+            check(lib().mnc_pileup_call_insertions(self._h, *args, out.ctypes.data, len(out), C.byref(n), bases.ctypes.data, len(bases), C.byref(nb)))
+        out = out[:n.value]
+        return out, [bases[int(o):int(o) + int(k)].tobytes() for o, k in zip(out["base_off"], out["len"])]
+
+    def add_insertions(self, rid, pos, count, bases):
+        """`mnc_pileup_add_insertion_list`: row i is `count[i]` observations of the allele `bases[i]` (bytes, on the hit's
+        strand) behind base `pos[i]` of contig `rid[i]` -- what `insertions()` of another accumulator returned, say."""
+        rid, pos, count = (np.ascontiguousarray(x, dtype=np.int32) for x in (rid, pos, count))
+        length = np.array([len(b) for b in bases], dtype=np.int32)
+        if not len(rid) == len(pos) == len(count) == len(length):
+            raise ValueError("rid, pos, count and bases must have one entry per row")
+        base_off = np.zeros(len(length), dtype=np.int64)
+        np.cumsum(length[:-1], out=base_off[1:])
+        flat = np.frombuffer(b"".join(bytes(b) for b in bases) or b"\0", dtype=np.uint8)
+        check(lib().mnc_pileup_add_insertion_list(self._h, len(rid), rid.ctypes.data, pos.ctypes.data, length.ctypes.data, count.ctypes.data,
+                                                  base_off.ctypes.data, flat.ctypes.data))
+
+    def consensus(self, rid, start=0, end=None, min_depth=1, insertions=False):
+        """One byte per base of [start, end) of contig `rid`: A C G T, '-' (deleted) or N (span < min_depth).  With
+        `insertions`, behind a base the majority insertion allele's bases in lower case (`mnc_pileup_consensus_ins`)."""
         end = self._end(rid, end)
+        if insertions:
+            n = C.c_int64(0)
+            args = (int(rid), int(start), end, int(min_depth))
+            rc = lib().mnc_pileup_consensus_ins(self._h, *args, None, 0, C.byref(n))
+            if rc not in (OK, ERR_RANGE) or not n.value:
+                check(rc)
+                return b""
+            out = np.zeros(n.value, dtype=np.uint8)
+            check(lib().mnc_pileup_consensus_ins(self._h, *args, out.ctypes.data, len(out), C.byref(n)))
+            return out[:n.value].tobytes()
         out = np.zeros(max(end - int(start), 0), dtype=np.uint8)
         check(lib().mnc_pileup_consensus(self._h, int(rid), int(start), end, int(min_depth), out.ctypes.data if len(out) else None))
         return out.tobytes()

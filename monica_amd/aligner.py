@@ -239,7 +239,10 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     min_count, min_permille) in place of `PILEUP_THRESHOLDS`, makes a per-base pileup for this sample and index part
     (`mappy_compat.Aligner.pileup`), adds every batch to it and leaves `<sample_name>.variants.tsv`
     (`VARIANTS_TSV_HEADER`, one row per called variant, positions 0-based) beside the coverage CSV.  It is collected with
-    `COV_GATED` per part, for the reason above: a variant file must not depend on which part came last.
+    `COV_GATED` per part, for the reason above: a variant file must not depend on which part came last.  A dict in its
+    place -- {"thresholds": (min_depth, min_count, min_permille), "insertions": (cap_alleles, cap_pool_bases)}, either key
+    optional -- also stores the inserted bases (`Pileup(insertions=)`): the file then has one row per called insertion
+    ALLELE, its `alt` a '+' followed by the bases, in place of the position's '+' row.
 
     Per batch: the library parses the FASTQ records (`mnc_fastq_next`), the GPU classifies them
     (`mnc_classify_batch`), the per-id hit lists carried over from earlier index parts are
@@ -272,7 +275,8 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     if coverage:
         cov = index.coverage(COVERAGE_BIN_BASES if coverage is True else int(coverage))
         cov_what = _capi.COV_ASSIGNED if last_index and not os.path.exists(carried_file) else _capi.COV_GATED
-    pile = index.pileup() if pileup else None
+    pile_thresholds, pile_insertions = pileup_options(pileup)
+    pile = index.pileup(insertions=pile_insertions) if pileup else None
     ab_args = {k: v for k, v in ab_opts.items() if k in ("cap_cands", "max_delta", "scale_q")}
     abund = index.abundance(**ab_args) if abundance and ab_across is None else None
     carry, reads_seen = None, [0]                         # (reads_seen: the file's reads classified so far, in file order)
@@ -549,8 +553,8 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
         write_coverage_csv(cov, os.path.join(out_folder, sample_name + ".coverage.csv"))
 
     def write_variants():
-        thresholds = PILEUP_THRESHOLDS if pileup is True else tuple(int(x) for x in pileup)
-        write_variants_tsv(index.index, pile.variants(-1, *thresholds), os.path.join(out_folder, sample_name + ".variants.tsv"))
+        alleles = pile.insertions(-1, *pile_thresholds) if pile_insertions is not None else None
+        write_variants_tsv(index.index, pile.variants(-1, *pile_thresholds), os.path.join(out_folder, sample_name + ".variants.tsv"), alleles)
 
     def write_abundance():
         write_abundance_csv(abund, os.path.join(mapped_folder, sample_name + ".abundance.csv"),
@@ -629,19 +633,37 @@ def write_abundance_csv(abund, path, **solve_args):
             out.write("{},{!r},{!r},{}\n".format(name, float(theta[g]), float(expected[g]), int(unique[g])))
 
 
-def write_variants_tsv(index, variants, path):
+def pileup_options(pileup):
+    """The `pileup=` argument as (thresholds, insertions): True, a 3-tuple of thresholds, or a dict with either key."""
+    opts = pileup if isinstance(pileup, dict) else {}
+    thresholds = PILEUP_THRESHOLDS if pileup is True or not pileup else opts.get("thresholds", PILEUP_THRESHOLDS) if opts else pileup
+    insertions = opts.get("insertions")
+    return tuple(int(x) for x in thresholds), None if insertions is None else tuple(int(x) for x in insertions)
+
+
+def write_variants_tsv(index, variants, path, insertions=None):
     """One row per called variant (`_capi.VARIANT_DTYPE`, as `Pileup.variants` returns them), appended to `path` (the
     header when the file is new): genome and contig by name, the 0-based position, reference and alternative allele
-    ('-' a deleted base, '+' an insertion behind `pos`), its count, the records over the base and count * 1000 // span."""
+    ('-' a deleted base, '+' an insertion behind `pos`), its count, the records over the base and count * 1000 // span.
+    With `insertions` (what `Pileup.insertions` returned at the same thresholds) a position's '+' row gives way to one row
+    per called insertion allele of that position, in their order, `alt` a '+' followed by the allele's bases."""
+    at = {}
+    if insertions is not None:
+        for rec, bases in zip(*insertions):
+            at.setdefault((int(rec["rid"]), int(rec["pos"])), []).append((bases.decode(), int(rec["count"]), int(rec["span"])))
     new = not os.path.exists(path) or not os.path.getsize(path)
     with open(path, "a") as out:
         if new:
             out.write("\t".join(VARIANTS_TSV_HEADER) + "\n")
         for v in variants:
             rid, count, span = int(v["rid"]), int(v["count"]), int(v["span"])
-            out.write("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(
-                index.genome_names[int(index.contig_genome[rid])], index.contig_names[rid], int(v["pos"]), v["ref"].decode(), v["alt"].decode(),
-                count, span, count * 1000 // span if span else 0))
+            rows = [(v["alt"].decode(), count, span)]
+            if insertions is not None and v["alt"] == b"+":
+                rows = [("+" + bases, c, s) for bases, c, s in at.get((rid, int(v["pos"])), [])]
+            for alt, count, span in rows:
+                out.write("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(
+                    index.genome_names[int(index.contig_genome[rid])], index.contig_names[rid], int(v["pos"]), v["ref"].decode(), alt,
+                    count, span, count * 1000 // span if span else 0))
 
 
 def _remove_consumed(sample):

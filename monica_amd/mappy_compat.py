@@ -332,9 +332,10 @@ class Aligner:
         """A coverage accumulator (`_capi.Coverage`) for this index on this object's device: pass it to `map_batch`."""
         return _capi.Coverage(self._index, self._device, bin_bases)
 
-    def pileup(self):
-        """A per-base pileup accumulator (`_capi.Pileup`) for this index on this object's device: pass it to `map_batch`."""
-        return _capi.Pileup(self._index, self._device)
+    def pileup(self, insertions=None):
+        """A per-base pileup accumulator (`_capi.Pileup`) for this index on this object's device: pass it to `map_batch`.
+        `insertions=(cap_alleles, cap_pool_bases)`: it stores the inserted bases too."""
+        return _capi.Pileup(self._index, self._device, insertions=insertions)
 
     def abundance(self, cap_cands=_capi.ABUNDANCE_CAP_CANDS, max_delta=_capi.ABUNDANCE_MAX_DELTA, scale_q=_capi.ABUNDANCE_SCALE_Q):
         """An abundance accumulator (`_capi.Abundance`) for this index on this object's device: pass it to `map_batch`,
