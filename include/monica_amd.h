@@ -196,6 +196,9 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   long alleles beyond cap_pool_bases           the allele keeps its exact count without bases and is counted in
  *                                                n_pool_dropped; the same two read-outs: MNC_ERR_RANGE until mnc_pileup_reset
  *   cap_alleles above 2^30                       mnc_pileup_store_insertions: MNC_ERR_ARG
+ *   min_qual outside 0 .. 93                     mnc_pileup_store_strands: MNC_ERR_ARG (a Phred+33 character holds no more)
+ *   qualities for a pileup without the strand    mnc_engine_add_pileup_quals: MNC_ERR_ARG; mnc_engine_add_pileup on a pileup with
+ *   store; no qualities for one that masks       min_qual > 0: MNC_ERR_ARG; after a call of both passes: MNC_ERR_UNSUPPORTED
  *   a reference base with 2^31 or more           outside the contract: every plane of mnc_pileup holds int32 per base
  *   observations in one pileup plane             (mnc_pileup_reset starts over)
  *   abundance after a call that ran both the     mnc_engine_add_abundance: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
@@ -550,14 +553,16 @@ typedef struct {
 	uint8_t pad[2];              /* 0 */
 } mnc_variant_t;
 /* MNC_ERR_NODEVICE without a gfx950 device, MNC_ERR_ARG for an index without contig bases, MNC_ERR_NOMEM when the 32 bytes
- * per reference base do not fit the HBM that is free (3.0 GB for an index of 94 Mbp). */
+ * per reference base do not fit the HBM that is free (3.0 GB for an index of 94 Mbp; mnc_pileup_store_strands makes them
+ * 72: 6.8 GB). */
 int  mnc_pileup_create(mnc_index *idx, int device, mnc_pileup **out);
 /* frees the accumulator and the HBM it holds (waits for the work queued on it) */
 void mnc_pileup_free(mnc_pileup *pu);
 /* clears every plane, and the insertion store if there is one; asynchronous */
 int  mnc_pileup_reset(mnc_pileup *pu);
 /* HBM the accumulator holds: 32 bytes per reference base, a few words per contig and 24 bytes per 1 024 bases of scratch;
- * with mnc_pileup_store_insertions 40 bytes per slot and the pool besides */
+ * with mnc_pileup_store_insertions 40 bytes per slot and the pool besides; with mnc_pileup_store_strands 40 more bytes per
+ * reference base (72 in all) */
 int  mnc_pileup_device_bytes(const mnc_pileup *pu, int64_t *bytes);
 /* The raw additive planes (device pointers), laid out as above; either pointer may be NULL.  Ordered behind the adds only
  * after a read-out call below or a sync of the engines that added. */
@@ -639,6 +644,69 @@ int  mnc_pileup_call_insertions(mnc_pileup *pu, int rid, int32_t min_depth, int3
  * (a tie: the first in the order above) iff span >= min_depth and 2 * count > span.  With its lower-case characters removed
  * the output is mnc_pileup_consensus of the interval.  *n = the characters; MNC_ERR_RANGE with *n set when cap is short. */
 int  mnc_pileup_consensus_ins(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t min_depth, char *out, int64_t cap, int64_t *n);
+
+/* ---- strands and base qualities (opt-in per accumulator; csrc/k_pile_strand.hip)
+ * The two standard filters against false variant calls on nanopore reads: an allele must be seen on both strands, because
+ * systematic errors are strand-specific, and a base below a quality floor is not evidence.  mnc_pileup_store_strands gives
+ * the accumulator the planes for both; a pileup that never calls it runs the add kernels it ran before, gives the same bits
+ * and allocates nothing.
+ *   forward        a record with rev == 0; reverse is total minus forward, plane by plane
+ *   masked         an M column whose read base has Phred < min_qual.  Phred is the quality character minus 33, clamped at 0;
+ *                  the read base of column p is qs + p for rev = 0 and qe - 1 - p for rev = 1 -- the base the column's
+ *                  observation is taken from.  A masked M column is tallied in neither the depth plane nor a base plane of ANY
+ *                  read-out; it is counted in MNC_PILE_LOWQ.  D columns and I operations have no quality and are never masked.
+ * One accumulator has one meaning: on a pileup with min_qual > 0, mnc_pileup_fetch_counts, mnc_pileup_call_variants,
+ * mnc_pileup_consensus, mnc_pileup_call_insertions and mnc_pileup_consensus_ins (through their spans) report the MASKED
+ * pileup.  With min_qual == 0 they equal a plain pileup's bit for bit.  The store may be combined with the insertion store;
+ * the allele table stays strand-less and unmasked.
+ * Storage: 40 more bytes of HBM per reference base, 72 in all, laid out as the planes of mnc_pileup_device:
+ *   d_track_fwd  int32[n_words]      depth differences of the forward records
+ *   d_alt_fwd    int32[7][n_words]   the forward records' channels
+ *   d_lowq       int32[2][n_words]   masked M columns: of both strands, of the forward records
+ * The depth differences are NOT broken at a masked column: depth = (sum of d_depth) - lowq, and likewise forward.  Every
+ * word is additive.  A reference match still costs no atomic; a forward record issues one more atomic wherever any record
+ * issues one, and a masked column costs one (two when forward), a reference match included.
+ * Called at most once, before the first add, as mnc_pileup_store_insertions: a call after an add, a second call, or
+ * min_qual outside 0 .. 93 is MNC_ERR_ARG.  min_qual = 0: no mask, and qualities are never needed.  mnc_pileup_reset clears
+ * the planes, mnc_pileup_device_bytes counts them. */
+#define MNC_PILE_FWD           (MNC_PILE_PLANES)           /* planes 8 .. 15: MNC_PILE_FWD + k is plane k of the forward records */
+#define MNC_PILE_LOWQ          (2 * MNC_PILE_PLANES)       /* plane 16: masked M columns */
+#define MNC_PILE_LOWQ_FWD      (2 * MNC_PILE_PLANES + 1)   /* plane 17: ... of the forward records */
+#define MNC_PILE_STRAND_PLANES (2 * MNC_PILE_PLANES + 2)   /* 18 */
+int  mnc_pileup_store_strands(mnc_pileup *pu, int32_t min_qual);
+/* mnc_engine_add_pileup with the batch's base qualities: `quals` are Phred+33 characters laid out by the offsets of the
+ * batch classified last -- what mnc_fastq_quals returns for that batch.  on_device = 0: a host pointer; the bytes are copied
+ * to a device buffer of the engine's (it grows on demand) on the engine's stream, in pieces as mnc_engine_prefetch queues
+ * its copy and for its reason, and the caller leaves the array alone until the engine's next synchronising call.
+ * on_device = 1: a device pointer, read as it is on the engine's stream.  Selectors, checks and ordering are
+ * mnc_engine_add_pileup's; a call that ran both the usual and the wide pass stays MNC_ERR_UNSUPPORTED -- it is also the
+ * case in which the offsets on the device are not the caller's.  With min_qual == 0 `quals` is not read and may be NULL.
+ *   mnc_engine_add_pileup_quals, pileup without a strand store    MNC_ERR_ARG
+ *   mnc_engine_add_pileup, pileup with min_qual > 0               MNC_ERR_ARG (this pileup masks by quality: add with qualities)
+ *   mnc_engine_add_pileup, strand store with min_qual == 0        adds, and fills the strand planes */
+int  mnc_engine_add_pileup_quals(mnc_engine *eng, mnc_pileup *pu, int what, const uint8_t *quals, int on_device);
+/* The 18 planes of bases [start, end) of contig rid, plane-major as mnc_pileup_fetch_counts writes its eight: planes 0 .. 7
+ * are those eight (both strands), planes MNC_PILE_FWD + k the same eight from forward records only, then MNC_PILE_LOWQ and
+ * MNC_PILE_LOWQ_FWD.  MNC_ERR_ARG without a strand store. */
+int  mnc_pileup_fetch_strand_counts(mnc_pileup *pu, int rid, int64_t start, int64_t end, int32_t *out /* [18][end - start] */);
+/* one called variant with its forward share (mnc_pileup_call_variants_strands): 28 bytes; reverse = total - forward */
+typedef struct {
+	int32_t rid, pos;
+	int32_t span;
+	int32_t count;
+	uint8_t ref;
+	uint8_t alt;
+	uint8_t pad[2];
+	int32_t count_fwd, span_fwd; /* the allele's observations and depth + del at pos, from forward records */
+} mnc_variant_strand_t;
+/* mnc_pileup_call_variants' rule and, on top of it, for each strand s (forward, reverse): count_s >= min_strand_count and
+ * count_s * 1000 >= min_strand_permille * span_s (int64).  Compaction, order and the MNC_ERR_RANGE protocol are
+ * mnc_pileup_call_variants'; with both strand thresholds 0 it yields exactly that call's records. */
+int  mnc_pileup_call_variants_strands(mnc_pileup *pu, int rid, int32_t min_depth, int32_t min_count, int32_t min_permille,
+                                      int32_t min_strand_count, int32_t min_strand_permille, mnc_variant_strand_t *out, int64_t cap, int64_t *n);
+/* The raw additive planes of the store (device pointers; any may be NULL), for a collective of the caller's, as
+ * mnc_pileup_device hands out the others: 10 * n_words more words.  MNC_ERR_ARG without a strand store. */
+int  mnc_pileup_strands_device(mnc_pileup *pu, const int32_t **d_track_fwd, const int32_t **d_alt_fwd, const int32_t **d_lowq);
 
 /* ---------------------------------------------------------------- abundance
  * Which of several close genomes is in the sample, and how much of each: the other half of the focus pass' question.  The

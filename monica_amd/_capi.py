@@ -46,6 +46,13 @@ COV_SUMMARY_DTYPE = np.dtype([("covered", "<i8"), ("depth_sum", "<i8"), ("max_de
 PILE_PLANES = ("depth", "A", "C", "G", "T", "N", "DEL", "INS")
 VARIANT_DTYPE = np.dtype([("rid", "<i4"), ("pos", "<i4"), ("span", "<i4"), ("count", "<i4"), ("ref", "S1"), ("alt", "S1"), ("pad", "<u2")])
 assert VARIANT_DTYPE.itemsize == 20
+# the planes of Pileup.strand_counts() (MNC_PILE_FWD + k, MNC_PILE_LOWQ, MNC_PILE_LOWQ_FWD) and one row of
+# Pileup.variants_strands() (mnc_variant_strand_t, 28 bytes: mnc_variant_t's fields, then the forward records' share)
+PILE_FWD, PILE_LOWQ, PILE_LOWQ_FWD = len(PILE_PLANES), 2 * len(PILE_PLANES), 2 * len(PILE_PLANES) + 1
+PILE_STRAND_PLANES = PILE_PLANES + tuple(p + "_fwd" for p in PILE_PLANES) + ("lowq", "lowq_fwd")
+VARIANT_STRAND_DTYPE = np.dtype(VARIANT_DTYPE.descr + [("count_fwd", "<i4"), ("span_fwd", "<i4")])
+assert VARIANT_STRAND_DTYPE.itemsize == 28 and len(PILE_STRAND_PLANES) == 18
+MAX_QUAL = 93                           # the largest Phred a Phred+33 character holds
 # one row of Pileup.insertions() (mnc_insertion_t, 32 bytes)
 INSERTION_DTYPE = np.dtype([("rid", "<i4"), ("pos", "<i4"), ("span", "<i4"), ("count", "<i4"), ("len", "<i4"), ("pad", "<i4"), ("base_off", "<i8")])
 assert INSERTION_DTYPE.itemsize == 32
@@ -90,6 +97,7 @@ EXPORTS = [
     "mnc_pileup_create", "mnc_pileup_free", "mnc_pileup_reset", "mnc_pileup_device_bytes", "mnc_pileup_device", "mnc_engine_add_pileup",
     "mnc_pileup_fetch_counts", "mnc_pileup_call_variants", "mnc_pileup_consensus",
     "mnc_pileup_store_insertions", "mnc_pileup_add_insertion_list", "mnc_pileup_insertion_info", "mnc_pileup_call_insertions", "mnc_pileup_consensus_ins",
+    "mnc_pileup_store_strands", "mnc_engine_add_pileup_quals", "mnc_pileup_fetch_strand_counts", "mnc_pileup_call_variants_strands", "mnc_pileup_strands_device",
     "mnc_abundance_create", "mnc_abundance_free", "mnc_abundance_reset", "mnc_abundance_device_bytes", "mnc_engine_add_abundance",
     "mnc_abundance_add_lists", "mnc_abundance_info", "mnc_abundance_fetch_unique", "mnc_abundance_fetch_lists", "mnc_abundance_solve",
     "mnc_abundance_device", "mnc_abundance_create_global", "mnc_abundance_add_carry",
@@ -249,6 +257,11 @@ def lib():
     sig("mnc_pileup_insertion_info", i32, [vp] + [C.POINTER(i64)] * 6)
     sig("mnc_pileup_call_insertions", i32, [vp, i32, i32, i32, i32, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)])
     sig("mnc_pileup_consensus_ins", i32, [vp, i32, i64, i64, i32, vp, i64, C.POINTER(i64)])
+    sig("mnc_pileup_store_strands", i32, [vp, i32])
+    sig("mnc_engine_add_pileup_quals", i32, [vp, vp, i32, vp, i32])
+    sig("mnc_pileup_fetch_strand_counts", i32, [vp, i32, i64, i64, vp])
+    sig("mnc_pileup_call_variants_strands", i32, [vp, i32, i32, i32, i32, i32, i32, vp, i64, C.POINTER(i64)])
+    sig("mnc_pileup_strands_device", i32, [vp, pp, pp, pp])
     sig("mnc_abundance_create", i32, [vp, i32, i64, C.c_int32, C.c_int32, pp])
     sig("mnc_abundance_free", None, [vp])
     sig("mnc_abundance_reset", i32, [vp])
@@ -550,6 +563,7 @@ class Engine:
 
     def sync(self):
         check(lib().mnc_engine_sync(self._h))
+        self._quals = None                                      # (add_pileup: the copy of the host array is over)
 
     def fetch_hits(self):
         """Gated hit lists of the last batch as CSR (offsets[n+1], hits)."""
@@ -605,10 +619,19 @@ class Engine:
         `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED, optionally | COV_SPAN.  Asynchronous."""
         self._add("mnc_engine_add_coverage", cov, int(what))
 
-    def add_pileup(self, pileup, what=COV_GATED):
+    def add_pileup(self, pileup, what=COV_GATED, quals=None, quals_on_device=False):
         """`mnc_engine_add_pileup`: add the last classified batch, as it stands in HBM, to the accumulator `pileup`.
-        `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
-        self._add("mnc_engine_add_pileup", pileup, int(what))
+        `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous.
+        `quals` (`mnc_engine_add_pileup_quals`, for a `Pileup(strands=)`): the batch's Phred+33 characters at the batch's
+        own offsets -- a uint8 array (`FastqReader.quals()`), or an address (a device one with `quals_on_device`).  A host
+        array is referenced here until `sync()`; memory given by address is the caller's to keep until then."""
+        if quals is None:
+            self._add("mnc_engine_add_pileup", pileup, int(what))
+            return
+        if not isinstance(quals, int):
+            quals = self._quals = np.ascontiguousarray(quals, dtype=np.uint8)
+            quals = quals.ctypes.data if quals.size else None
+        self._add("mnc_engine_add_pileup_quals", pileup, int(what), quals, 1 if quals_on_device else 0)
 
     def add_abundance(self, abundance):
         """`mnc_engine_add_abundance`: add the candidate genomes of every read of the last classified batch, as it stands in
@@ -772,21 +795,26 @@ class Pileup(_Accumulator):
     """Owner of an ``mnc_pileup``: what the reads say at every reference base of one index on one device -- depth, the
     counts of A C G T N, deletions and insertions -- accumulated from batch to batch by `Engine.add_pileup`
     (include/monica_amd.h, "pileup").  `insertions=(cap_alleles, cap_pool_bases)` makes it store the inserted bases too
-    (`mnc_pileup_store_insertions`): `insertions()`, `insertion_info()`, `add_insertions()`, `consensus(insertions=True)`."""
+    (`mnc_pileup_store_insertions`): `insertions()`, `insertion_info()`, `add_insertions()`, `consensus(insertions=True)`.
+    `strands=min_qual` (0 .. MAX_QUAL; 0: no mask) gives it the strand store (`mnc_pileup_store_strands`): the forward
+    records' own planes and, for min_qual > 0, a mask of the M columns whose base quality is below it -- `strand_counts()`,
+    `variants_strands()`, `strands_device()`; every other read-out then reports the masked pileup."""
 
     _c = "pileup"
 
-    def __init__(self, index, device=0, insertions=None):
+    def __init__(self, index, device=0, insertions=None, strands=None):
         self.index = index
         self._device = device                                   # (`device` is the method below)
         self._create(index, device)
-        if insertions is not None:
-            cap_alleles, cap_pool_bases = insertions
-            try:
+        try:
+            if insertions is not None:
+                cap_alleles, cap_pool_bases = insertions
                 check(lib().mnc_pileup_store_insertions(self._h, int(cap_alleles), int(cap_pool_bases)))
-            except BaseException:
-                self.close()
-                raise
+            if strands is not None:
+                check(lib().mnc_pileup_store_strands(self._h, int(strands)))
+        except BaseException:
+            self.close()
+            raise
 
     def _end(self, rid, end):
         return (self.index.contig_lens[rid] if 0 <= rid < len(self.index.contig_lens) else 0) if end is None else int(end)
@@ -809,6 +837,34 @@ class Pileup(_Accumulator):
         if len(out):
             check(lib().mnc_pileup_call_variants(self._h, *args, out.ctypes.data, len(out), C.byref(n)))
         return out[:n.value]
+
+    def strand_counts(self, rid, start=0, end=None):
+        """The 18 planes (PILE_STRAND_PLANES) of bases [start, end) of contig `rid`: int32[18, end - start] -- the eight of
+        `counts()`, the same eight from forward records (PILE_FWD + k), the masked columns (PILE_LOWQ, PILE_LOWQ_FWD)."""
+        end = self._end(rid, end)
+        out = np.zeros((len(PILE_STRAND_PLANES), max(end - int(start), 0)), dtype=np.int32)
+        check(lib().mnc_pileup_fetch_strand_counts(self._h, int(rid), int(start), end, out.ctypes.data if out.size else None))
+        return out
+
+    def variants_strands(self, rid=-1, min_depth=1, min_count=1, min_permille=0, min_strand_count=0, min_strand_permille=0):
+        """`variants()` with the strand filter (VARIANT_STRAND_DTYPE): on each strand the allele has `min_strand_count`
+        observations and `min_strand_permille` of that strand's span."""
+        n = C.c_int64(0)
+        args = tuple(int(x) for x in (rid, min_depth, min_count, min_permille, min_strand_count, min_strand_permille))
+        rc = lib().mnc_pileup_call_variants_strands(self._h, *args, None, 0, C.byref(n))
+        if rc not in (OK, ERR_RANGE):
+            check(rc)
+        out = np.zeros(n.value, dtype=VARIANT_STRAND_DTYPE)
+        if len(out):
+            check(lib().mnc_pileup_call_variants_strands(self._h, *args, out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
+    def strands_device(self):
+        """(device address of the forward depth differences, of the seven forward alt planes, of the two planes of masked
+        columns): `mnc_pileup_strands_device`."""
+        t, a, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().mnc_pileup_strands_device(self._h, C.byref(t), C.byref(a), C.byref(q)))
+        return int(t.value or 0), int(a.value or 0), int(q.value or 0)
 
     def insertion_info(self):
         """`mnc_pileup_insertion_info` as a dict: n_alleles, n_events, n_dropped, n_pool_bases, n_pool_dropped, n_collisions."""

@@ -242,7 +242,10 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     `COV_GATED` per part, for the reason above: a variant file must not depend on which part came last.  A dict in its
     place -- {"thresholds": (min_depth, min_count, min_permille), "insertions": (cap_alleles, cap_pool_bases)}, either key
     optional -- also stores the inserted bases (`Pileup(insertions=)`): the file then has one row per called insertion
-    ALLELE, its `alt` a '+' followed by the bases, in place of the position's '+' row.
+    ALLELE, its `alt` a '+' followed by the bases, in place of the position's '+' row.  The dict may also carry
+    "strands": True and / or "min_qual": q (`Pileup(strands=)`; the reader's base qualities go with every batch, and an
+    M column below Phred q is no evidence), "min_strand_count": c and "min_strand_permille": m (the allele is seen c times,
+    and in m permille of the span, on EACH strand): the file then has two more columns, `count_fwd` and `span_fwd`.
 
     Per batch: the library parses the FASTQ records (`mnc_fastq_next`), the GPU classifies them
     (`mnc_classify_batch`), the per-id hit lists carried over from earlier index parts are
@@ -276,7 +279,8 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
         cov = index.coverage(COVERAGE_BIN_BASES if coverage is True else int(coverage))
         cov_what = _capi.COV_ASSIGNED if last_index and not os.path.exists(carried_file) else _capi.COV_GATED
     pile_thresholds, pile_insertions = pileup_options(pileup)
-    pile = index.pileup(insertions=pile_insertions) if pileup else None
+    pile_strands = pileup_strand_options(pileup)
+    pile = index.pileup(insertions=pile_insertions, strands=pile_strands and pile_strands[0]) if pileup else None
     ab_args = {k: v for k, v in ab_opts.items() if k in ("cap_cands", "max_delta", "scale_q")}
     abund = index.abundance(**ab_args) if abundance and ab_across is None else None
     carry, reads_seen = None, [0]                         # (reads_seen: the file's reads classified so far, in file order)
@@ -286,6 +290,15 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
         carry = ab_across["carry"]
         genome_offset = len(ab_across["names"])
 
+    def pile_batch(batch):
+        if pile_strands and pile_strands[0] > 0:
+            # the batch's own quality characters; the engine copies them behind the batch's kernels, and the batch is
+            # closed once it is routed -- so the copy is waited for here
+            engine.add_pileup(pile, _capi.COV_GATED, quals=batch.quals())
+            engine.sync()
+        else:
+            engine.add_pileup(pile, _capi.COV_GATED)
+
     def carry_batch(batch):
         carry.reserve(reads_seen[0] + batch.n)
         engine.carry_candidates(carry, reads_seen[0], genome_offset)
@@ -293,7 +306,7 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
     # what every classified batch is added to (asynchronously, behind the batch's kernels), and what a message calls it
     adds = [(add, noun) for accum, add, noun in (
         (cov, lambda batch: engine.add_coverage(cov, cov_what), "coverage"),
-        (pile, lambda batch: engine.add_pileup(pile, _capi.COV_GATED), "pileup"),
+        (pile, pile_batch, "pileup"),
         (abund, lambda batch: engine.add_abundance(abund), "abundance candidates"),
         (carry, carry_batch, "abundance candidates")) if accum is not None]
 
@@ -554,7 +567,8 @@ def aligner_coverage(sample, sample_name, index, mode=None, hits_folder=None, ma
 
     def write_variants():
         alleles = pile.insertions(-1, *pile_thresholds) if pile_insertions is not None else None
-        write_variants_tsv(index.index, pile.variants(-1, *pile_thresholds), os.path.join(out_folder, sample_name + ".variants.tsv"), alleles)
+        called = pile.variants_strands(-1, *pile_thresholds, *pile_strands[1:]) if pile_strands else pile.variants(-1, *pile_thresholds)
+        write_variants_tsv(index.index, called, os.path.join(out_folder, sample_name + ".variants.tsv"), alleles)
 
     def write_abundance():
         write_abundance_csv(abund, os.path.join(mapped_folder, sample_name + ".abundance.csv"),
@@ -641,12 +655,28 @@ def pileup_options(pileup):
     return tuple(int(x) for x in thresholds), None if insertions is None else tuple(int(x) for x in insertions)
 
 
+def pileup_strand_options(pileup):
+    """The strand part of a `pileup=` dict: None without it, else (min_qual, min_strand_count, min_strand_permille).  Any of
+    "strands": True, "min_qual", "min_strand_count" and "min_strand_permille" asks for the strand store."""
+    opts = pileup if isinstance(pileup, dict) else {}
+    keys = ("min_qual", "min_strand_count", "min_strand_permille")
+    if not opts.get("strands") and not any(k in opts for k in keys):
+        return None
+    out = tuple(int(opts.get(k, 0)) for k in keys)
+    if not 0 <= out[0] <= _capi.MAX_QUAL or min(out[1:]) < 0:
+        raise ValueError(f"pileup=: min_qual {out[0]} (0 .. {_capi.MAX_QUAL}), min_strand_count {out[1]}, min_strand_permille {out[2]} (0 or more)")
+    return out
+
+
 def write_variants_tsv(index, variants, path, insertions=None):
     """One row per called variant (`_capi.VARIANT_DTYPE`, as `Pileup.variants` returns them), appended to `path` (the
     header when the file is new): genome and contig by name, the 0-based position, reference and alternative allele
     ('-' a deleted base, '+' an insertion behind `pos`), its count, the records over the base and count * 1000 // span.
     With `insertions` (what `Pileup.insertions` returned at the same thresholds) a position's '+' row gives way to one row
-    per called insertion allele of that position, in their order, `alt` a '+' followed by the allele's bases."""
+    per called insertion allele of that position, in their order, `alt` a '+' followed by the allele's bases.
+    Rows of `_capi.VARIANT_STRAND_DTYPE` (`Pileup.variants_strands`) get two more columns: `count_fwd` and `span_fwd`, the
+    share of forward records (an insertion allele's row repeats its position's)."""
+    by_strand = "count_fwd" in (variants.dtype.names or ())
     at = {}
     if insertions is not None:
         for rec, bases in zip(*insertions):
@@ -654,14 +684,15 @@ def write_variants_tsv(index, variants, path, insertions=None):
     new = not os.path.exists(path) or not os.path.getsize(path)
     with open(path, "a") as out:
         if new:
-            out.write("\t".join(VARIANTS_TSV_HEADER) + "\n")
+            out.write("\t".join(tuple(VARIANTS_TSV_HEADER) + (("count_fwd", "span_fwd") if by_strand else ())) + "\n")
         for v in variants:
+            tail = "\t{}\t{}\n".format(int(v["count_fwd"]), int(v["span_fwd"])) if by_strand else "\n"
             rid, count, span = int(v["rid"]), int(v["count"]), int(v["span"])
             rows = [(v["alt"].decode(), count, span)]
             if insertions is not None and v["alt"] == b"+":
                 rows = [("+" + bases, c, s) for bases, c, s in at.get((rid, int(v["pos"])), [])]
             for alt, count, span in rows:
-                out.write("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(
+                out.write(("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}" + tail).format(
                     index.genome_names[int(index.contig_genome[rid])], index.contig_names[rid], int(v["pos"]), v["ref"].decode(), alt,
                     count, span, count * 1000 // span if span else 0))
 

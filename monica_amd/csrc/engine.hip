@@ -102,7 +102,9 @@ const Accum *as_accum(const mnc_coverage *cv);
 const Accum *as_accum(const mnc_pileup *pu);
 const Accum *as_accum(const mnc_abundance *ab);
 int coverage_add(mnc_coverage *cv, const Batch &B, int sel, bool span, hipStream_t st);
-int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st);
+int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st, const uint8_t *d_quals);
+int pileup_quals_check(const mnc_pileup *pu, bool with_quals);   // k_pile_strand.hip
+int pileup_min_qual(const mnc_pileup *pu);
 int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st);
 // the candidate carry (k_carry.hip): an Accum of a device, of no index
 const Accum *as_accum(const mnc_carry *cc);
@@ -427,6 +429,7 @@ struct mnc_engine {
 	Buf in_bases, in_offsets, out_assign, out_best, out_nhits;
 	// the next batch's bases on their way to the device while this one is classified (mnc_engine_prefetch)
 	Buf pf_bases_buf, pf_offsets_buf;
+	Buf quals_buf;                           // the last batch's quality characters (mnc_engine_add_pileup_quals with a host pointer)
 	hipStream_t copy_stream = nullptr;
 	hipEvent_t ev_prefetch = nullptr;
 	std::mutex pf_mu;
@@ -580,7 +583,7 @@ extern "C" int mnc_device_name(int device, char *buf, size_t cap)
 template <class F> static void engine_bufs(mnc_engine *e, F f)
 {
 	Buf *all[] = { &e->gap_lut, &e->logf_lut, &e->logf_a_lut, &e->ca, &e->ca_cnt, &e->chain_dst, &e->regdp, &e->segs, &e->cig_seg, &e->cig_reg, &e->dp_ctr,
-	               &e->work_a, &e->work_b, &e->big_list, &e->huge_list, &e->reg_cnt, &e->regs2, &e->inv_ws, &e->fill1, &e->fill2, &e->fill3, &e->fill_mid, &e->fill_fb, &e->plan_long, &e->extp, &e->mid_list, &e->lfill, &e->lext, &e->bigfb, &e->ext1, &e->ext2, &e->ext3, &e->ext4, &e->gen_list, &e->in_bases, &e->in_offsets, &e->pf_bases_buf, &e->pf_offsets_buf, &e->out_assign, &e->out_best, &e->out_nhits,
+	               &e->work_a, &e->work_b, &e->big_list, &e->huge_list, &e->reg_cnt, &e->regs2, &e->inv_ws, &e->fill1, &e->fill2, &e->fill3, &e->fill_mid, &e->fill_fb, &e->plan_long, &e->extp, &e->mid_list, &e->lfill, &e->lext, &e->bigfb, &e->ext1, &e->ext2, &e->ext3, &e->ext4, &e->gen_list, &e->in_bases, &e->in_offsets, &e->pf_bases_buf, &e->pf_offsets_buf, &e->quals_buf, &e->out_assign, &e->out_best, &e->out_nhits,
 	               &e->packed, &e->mz, &e->hits, &e->hist_tm, &e->q_off, &e->qrec, &e->bhits, &e->bhit_cnt, &e->ambig, &e->skip, &e->mz_cnt, &e->hit_cnt, &e->rep_len, &e->an_cnt, &e->an_off,
 	               &e->n_chain, &e->n_reg, &e->best_mlen, &e->hist_sums, &e->hist_offs, &e->scan_sums, &e->hit_off, &e->a, &e->f, &e->p, &e->v, &e->t, &e->u,
 	               &e->chains_tmp, &e->regs, &e->regx, &e->k64a, &e->k64b, &e->tmp_i32, &e->gated,
@@ -1779,9 +1782,37 @@ extern "C" int mnc_engine_add_pileup(mnc_engine *e, mnc_pileup *pu, int what)
 	int sel = 0;
 	if (int rc = add_selector(what, true, &sel)) return rc;
 	if (int rc = add_precheck(e, as_accum(pu), "pileup", "a pileup needs the CIGARs of MNC_CONTRACT_DP")) return rc;
+	if (int rc = pileup_quals_check(pu, false)) return rc;
 	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
-	return pileup_add(pu, e->B, sel, e->stream);
+	return pileup_add(pu, e->B, sel, e->stream, nullptr);
+}
+
+// ... with the batch's quality characters, for a pileup with the strand store (k_pile_strand.hip).  A host array goes to a
+// buffer of the engine's on the engine's stream, so the add kernel comes behind the copy and the next call's copy behind
+// the kernel.  In pieces, as mnc_engine_prefetch queues its copy: the batch's small read-backs must not wait behind it.
+extern "C" int mnc_engine_add_pileup_quals(mnc_engine *e, mnc_pileup *pu, int what, const uint8_t *quals, int on_device)
+{
+	if (!e || !pu) return MNC_ERR_ARG;
+	int sel = 0;
+	if (int rc = add_selector(what, true, &sel)) return rc;
+	if (int rc = add_precheck(e, as_accum(pu), "pileup", "a pileup needs the CIGARs of MNC_CONTRACT_DP")) return rc;
+	if (int rc = pileup_quals_check(pu, true)) return rc;
+	if (e->B.n_reads == 0) return MNC_OK;
+	const size_t total = (size_t)e->B.total_bases;
+	const bool masks = pileup_min_qual(pu) > 0;                 // without a mask the qualities are never needed
+	if (masks && total && !quals) { set_error("this pileup masks by quality: `quals` is NULL"); return MNC_ERR_ARG; }
+	HIP_TRY(hipSetDevice(e->device));
+	const uint8_t *d_quals = masks ? quals : nullptr;
+	if (masks && !on_device) {
+		if (total + 32 > e->quals_buf.cap) HIP_TRY(hipStreamSynchronize(e->stream));   // an earlier add may still read the buffer that is let go
+		if (int rc = e->quals_buf.ensure(total + 32)) return rc;
+		constexpr size_t PIECE = 4u << 20;
+		for (size_t o = 0; o < total; o += PIECE)
+			HIP_TRY(hipMemcpyAsync(e->quals_buf.as<uint8_t>() + o, quals + o, std::min(PIECE, total - o), hipMemcpyHostToDevice, e->stream));
+		d_quals = e->quals_buf.as<uint8_t>();
+	}
+	return pileup_add(pu, e->B, sel, e->stream, d_quals);
 }
 
 // ---------------------------------------------------------------- abundance candidates of the last batch

@@ -27,6 +27,8 @@
 //                   the consensus; variants take MODE 1 (calls per tile), scan.h's exclusive scan over the tiles, and MODE 2
 //                   (each tile places its records behind its offset by a prefix sum over its threads): compacted and in
 //                   (contig, position, allele) order without a per-base offset array.
+// With the strand store (mnc_pileup_store_strands) the add and the read-outs by strand are k_pile_strand.hip's; the read-outs
+// here then see a nullable plane of masked columns (PileView::lowq) and nothing else of it.
 #include <hip/hip_runtime.h>
 #include <new>
 #include <vector>
@@ -49,12 +51,13 @@ __global__ __launch_bounds__(256) void mnc_pile_add(Batch B, int sel, const int6
 const Accum *as_accum(const mnc_pileup *pu) { return pu; }
 
 // the batch B, as it stands in HBM, on the engine's stream `st`; nothing waits on the host
-int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st)
+int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st, const uint8_t *d_quals)
 {
 	if (B.n_reads == 0 || pu->n_words == 0) return MNC_OK;
 	return pu->add(st, [&] {
 		pu->added = true;
-		if (pu->ins_on) pileup_add_ins_launch(pu, B, sel, st);
+		if (pu->strands_on) pileup_add_strands_launch(pu, B, sel, st, d_quals);
+		else if (pu->ins_on) pileup_add_ins_launch(pu, B, sel, st);
 		else
 			hipLaunchKernelGGL(mnc_pile_add, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, pu->d_off, pu->n_contigs, pu->n_words, pu->track, pu->alt);
 	});
@@ -97,7 +100,7 @@ extern "C" int mnc_pileup_create(mnc_index *idx, int device, mnc_pileup **out)
 	pu->streams(he);
 	if (he == hipSuccess) he = hipMemcpy(pu->d_off, pu->off.data(), (nc + 1) * 8, hipMemcpyHostToDevice);
 	if (he != hipSuccess) {
-		set_error("pileup accumulator of %lld bases (32 bytes each): %s", (long long)pu->n_words, hipGetErrorString(he));
+		set_error("pileup accumulator of %lld bases (32 bytes each; 72 with the strand store): %s", (long long)pu->n_words, hipGetErrorString(he));
 		const int rc = Accum::failed(he);
 		mnc_pileup_free(pu);
 		return rc;
@@ -117,6 +120,7 @@ extern "C" int mnc_pileup_reset(mnc_pileup *pu)
 		HIP_TRY(hipMemsetAsync(pu->alt, 0, (size_t)pu->n_words * 4 * PILE_ALT, pu->st));
 	}
 	if (pu->ins_on) HIP_TRY(ins_clear(pu));
+	if (pu->strands_on) HIP_TRY(strands_clear(pu));
 	HIP_TRY(pu->own_done());
 	return MNC_OK;
 }

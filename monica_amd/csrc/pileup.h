@@ -1,7 +1,8 @@
 // What the two units of the pileup share (k_pileup.hip: the planes, their add kernel and read-outs; k_pile_ins.hip: the
 // insertion store's kernels and read-outs): the accumulator's struct, the walk of one read's records with one lane per
 // column (pile_add_read; <true> also hands every I operation to the store), and the read-outs' pass over the tiles
-// (mnc_pile_scan).  k_pileup.hip's header comment describes them.
+// (mnc_pile_scan).  k_pileup.hip's header comment describes them.  A third unit, k_pile_strand.hip, holds the opt-in strand
+// store: the same walk with the forward records' own planes and a base-quality mask, and the read-outs by strand.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,6 +32,16 @@ struct mnc_pileup : mnc::Accum {
 	bool ins_on = false;                       // mnc_pileup_store_insertions was called: `ins` is the allele table (pile_ins.h)
 	bool added = false;                        // something has been added since creation (under `mu`)
 	mnc::InsTable ins{};
+	// ---- the strand store (mnc_pileup_store_strands, k_pile_strand.hip): 40 more bytes per reference base
+	bool strands_on = false;
+	int min_qual = 0;                          // an M column whose read base has a Phred below it is masked; 0: no mask
+	int32_t *track_f = nullptr;                // [n_words] depth differences of the forward records
+	int32_t *alt_f = nullptr;                  // [PILE_ALT][n_words] ... and their channels
+	int32_t *lowq = nullptr;                   // [2][n_words] masked M columns: of both strands, of the forward records
+	long long *cbase_f = nullptr;              // cbase and tile_sums once more, for track_f (scratch)
+	int64_t *tile_sums_f = nullptr;
+	// what the read-outs of both strands subtract from the depth: nothing without a mask (today's code)
+	const int32_t *lowq_view() const { return min_qual > 0 ? lowq : nullptr; }
 };
 
 namespace mnc {
@@ -48,10 +59,24 @@ __device__ __forceinline__ void pile_put(int32_t *plane, int64_t len, int64_t po
 	if (pos >= 0 && pos < len) (void)__hip_atomic_fetch_add(plane + pos, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the strand store's side of the add (k_pile_strand.hip): its planes, and the batch's quality characters (Phred + 33, laid
+// out as the bases are) with the floor below which an M column is masked
+struct PileStrands {
+	int32_t *track_f, *alt_f, *lowq;
+	const uint8_t *quals;
+	int min_qual;
+};
+
 // INS: the insertion store is on -- the lane of an I column hands its operation to ins_wave_add (pile_ins.h), and that is
-// all the difference: the planes get what they get without it
-template <bool INS>
-__device__ __forceinline__ void pile_add_read(const Batch &B, int sel, const int64_t *off, int n_contigs, int64_t n_words, int32_t *track, int32_t *alt, const InsTable &T)
+// all the difference: the planes get what they get without it.
+// STR: the strand store is on -- a forward record (wave-uniform: a wave holds one read, and `rev` is the record's) repeats
+// its depth runs in track_f and every atomic it issues on `alt` in alt_f.  QUAL: an M lane also loads the quality byte of
+// its read base; below the floor it issues no `alt` atomic, match or not, and counts the column in lowq (and lowq's forward
+// half).  The depth runs are NOT broken at a masked column: the read-outs subtract lowq.  Without STR and QUAL nothing of
+// this is instantiated.
+template <bool INS, bool STR = false, bool QUAL = false>
+__device__ __forceinline__ void pile_add_read(const Batch &B, int sel, const int64_t *off, int n_contigs, int64_t n_words, int32_t *track, int32_t *alt, const InsTable &T,
+                                              const PileStrands &S = PileStrands{})
 {
 	const int lane = lane_id();
 	const uint32_t rd = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -65,16 +90,26 @@ __device__ __forceinline__ void pile_add_read(const Batch &B, int sel, const int
 		if (n_c <= 0) return;
 		const int64_t coff = off[r.rid], len = off[r.rid + 1] - coff;
 		int32_t *w = track + coff, *a = alt + coff;            // channel ch of base p: a[ch * n_words + p]
+		const bool fwd = STR && !r.rev;
+		int32_t *wf = STR ? S.track_f + coff : nullptr, *af = STR ? S.alt_f + coff : nullptr, *lq = QUAL ? S.lowq + coff : nullptr;
 		const uint32_t *src = B.cig_reg + B.regdp[slot].cig_off;
+		auto At = [&](int p) -> int {                           // the read base of column p of the query side
+			const int at = r.rev ? r.qe - 1 - p : r.qs + p;
+			return at < 0 ? 0 : at >= qlen ? qlen - 1 : at;
+		};
 		auto Q = [&](int p) -> int {                            // column p of the query side, on the hit's strand (k_export.hip)
-			int at = r.rev ? r.qe - 1 - p : r.qs + p;
-			at = at < 0 ? 0 : at >= qlen ? qlen - 1 : at;
-			const int c = base_nt4(read[at]);
+			const int c = base_nt4(read[At(p)]);
 			return r.rev ? (c < 4 ? 3 - c : 4) : c;
+		};
+		// one observation of channel ch at base p; a forward record's goes to its own planes as well
+		auto put = [&](int ch, int64_t p) {
+			pile_put(a + (int64_t)ch * n_words, len, p);
+			if (fwd) pile_put(af + (int64_t)ch * n_words, len, p);
 		};
 		int64_t toff = r.rs;                                   // reference position before the chunk at hand
 		int qoff = 0;                                          // query columns before it
 		bool open = false;                                     // a run is open: the last M / D operation so far was an M
+		bool open_f = false;                                   // STR: the same for the forward track
 		int claims = 0;                                        // INS: the alleles this wave has claimed in this record (pile_ins.h)
 		for (int k0 = 0; k0 < n_c; k0 += 64) {
 			const bool full = INS && ins_full(T);
@@ -88,6 +123,7 @@ __device__ __forceinline__ void pile_add_read(const Batch &B, int sel, const int
 			const int my_t0 = it - dt, my_q0 = qoff + iq - dq;    // (the reference offset within the chunk: toff is 64 bits)
 			// ---- depth: the runs of M columns
 			cov_run_step(w, len, l > 0 && op == 0, l > 0 && op == 2, toff + my_t0, open);
+			if (fwd) cov_run_step(wf, len, l > 0 && op == 0, l > 0 && op == 2, toff + my_t0, open_f);
 			// ---- the columns, one lane each
 			const int total = __shfl(ie, 63);
 			for (int c0 = 0; c0 < total; c0 += 64) {
@@ -107,12 +143,22 @@ __device__ __forceinline__ void pile_add_read(const Batch &B, int sel, const int
 				if (valid) {
 					if (o_op == 0) {
 						if (p >= 0 && p < len) {
-							const int qc = Q(q0 + x), tc = pile_ref(B.seq4, coff + p);
-							if (tc == 4 || qc != tc) pile_put(a + (int64_t)qc * n_words, len, p);
+							bool masked = false;
+							if (QUAL) {
+								const int phred = (int)S.quals[read_off + At(q0 + x)] - 33;   // (below '!': Phred 0)
+								masked = phred < S.min_qual;
+							}
+							if (masked) {
+								pile_put(lq, len, p);
+								if (fwd) pile_put(lq + n_words, len, p);
+							} else {
+								const int qc = Q(q0 + x), tc = pile_ref(B.seq4, coff + p);
+								if (tc == 4 || qc != tc) put(qc, p);
+							}
 						}
-					} else if (o_op == 2) pile_put(a + (int64_t)CH_DEL * n_words, len, p);
+					} else if (o_op == 2) put(CH_DEL, p);
 					else if (p > r.rs) {                                 // a reference column of this record lies on its left
-						pile_put(a + (int64_t)CH_INS * n_words, len, p - 1);
+						put(CH_INS, p - 1);
 						stored = p - 1 >= 0 && p - 1 < len;
 					}
 				}
@@ -122,6 +168,7 @@ __device__ __forceinline__ void pile_add_read(const Batch &B, int sel, const int
 			toff += __shfl(it, 63), qoff += __shfl(iq, 63);
 		}
 		cov_run_close(w, len, toff, open);
+		if (fwd) cov_run_close(wf, len, toff, open_f);
 		if (INS) ins_flush(T, claims);
 	});
 }
@@ -133,6 +180,7 @@ struct PileView {
 	const uint32_t *seq4;
 	const int64_t *off;
 	int n_contigs;
+	const int32_t *lowq = nullptr;            // the masked M columns of a pileup that masks by quality: taken off the depth
 };
 struct PileThr {
 	int min_depth, min_count, min_permille;
@@ -149,6 +197,7 @@ struct PileBase {
 __device__ __forceinline__ PileBase pile_load(const PileView &P, int64_t g, int depth)
 {
 	PileBase b;
+	if (P.lowq) depth -= P.lowq[g];
 	for (int ch = 0; ch < PILE_ALT; ++ch) b.cnt[ch] = P.alt[(int64_t)ch * P.n_words + g];
 	b.depth = depth, b.ref = pile_ref(P.seq4, g);
 	if (b.ref < 4) b.cnt[b.ref] += depth - (b.cnt[0] + b.cnt[1] + b.cnt[2] + b.cnt[3] + b.cnt[CH_N]);
@@ -274,7 +323,7 @@ template <int MODE>
 static inline void pile_launch(mnc_pileup *pu, int64_t w0, int64_t n, bool all, int rid, int64_t start, PileThr thr, int32_t *o_counts, mnc_variant_t *o_var,
                         int64_t var_cap, char *o_cons)
 {
-	const PileView P{pu->track, pu->alt, pu->n_words, pu->didx->seq4, pu->d_off, pu->n_contigs};
+	const PileView P{pu->track, pu->alt, pu->n_words, pu->didx->seq4, pu->d_off, pu->n_contigs, pu->lowq_view()};
 	hipLaunchKernelGGL(mnc_pile_scan<MODE>, dim3((unsigned)((n + SC_TILE - 1) / SC_TILE)), dim3(SC_THREADS), 0, pu->st, P, w0, n, pu->tile_sums,
 	                   all ? pu->cbase : nullptr, rid, start, thr, o_counts, pu->tile_cnt, pu->tile_voff, o_var, var_cap, o_cons);
 }
@@ -283,5 +332,9 @@ static inline void pile_launch(mnc_pileup *pu, int64_t w0, int64_t n, bool all, 
 // the table on the accumulator's own stream
 void pileup_add_ins_launch(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st);
 hipError_t ins_clear(mnc_pileup *pu);
+// k_pile_strand.hip: the add of a pileup with the strand store (d_quals: the batch's quality characters on the device, or
+// nullptr where there is no mask), the clearing of its planes on the accumulator's own stream, and what an add checks first
+void pileup_add_strands_launch(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st, const uint8_t *d_quals);
+hipError_t strands_clear(mnc_pileup *pu);
 
 } // namespace mnc

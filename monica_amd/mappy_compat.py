@@ -332,10 +332,11 @@ class Aligner:
         """A coverage accumulator (`_capi.Coverage`) for this index on this object's device: pass it to `map_batch`."""
         return _capi.Coverage(self._index, self._device, bin_bases)
 
-    def pileup(self, insertions=None):
+    def pileup(self, insertions=None, strands=None):
         """A per-base pileup accumulator (`_capi.Pileup`) for this index on this object's device: pass it to `map_batch`.
-        `insertions=(cap_alleles, cap_pool_bases)`: it stores the inserted bases too."""
-        return _capi.Pileup(self._index, self._device, insertions=insertions)
+        `insertions=(cap_alleles, cap_pool_bases)`: it stores the inserted bases too.  `strands=min_qual`: it keeps the
+        forward records' counts apart and masks M columns below that base quality (`map_batch(quals=)`)."""
+        return _capi.Pileup(self._index, self._device, insertions=insertions, strands=strands)
 
     def abundance(self, cap_cands=_capi.ABUNDANCE_CAP_CANDS, max_delta=_capi.ABUNDANCE_MAX_DELTA, scale_q=_capi.ABUNDANCE_SCALE_Q):
         """An abundance accumulator (`_capi.Abundance`) for this index on this object's device: pass it to `map_batch`,
@@ -352,13 +353,14 @@ class Aligner:
         return _capi.Abundance.global_(self._device, len(genome_names), cap_cands, max_delta, scale_q, genome_names=genome_names)
 
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
-                  abundance=None):
+                  abundance=None, quals=None):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
         added to it -- `coverage_what`: one `_capi.COV_*` selector, optionally | COV_SPAN -- before the hits are fetched; with
         `pileup` (an accumulator of `pileup()`) likewise, `pileup_what` one selector; with `abundance` (an accumulator of
-        `abundance()`) every read's candidate genomes are added to it."""
+        `abundance()`) every read's candidate genomes are added to it.  `quals`: the batch's Phred+33 characters at
+        `offsets`, for a `pileup(strands=min_qual)` that masks by base quality."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -370,7 +372,7 @@ class Aligner:
         if coverage is not None:
             eng.add_coverage(coverage, coverage_what)
         if pileup is not None:
-            eng.add_pileup(pileup, pileup_what)
+            eng.add_pileup(pileup, pileup_what, quals=quals)
         if abundance is not None:
             eng.add_abundance(abundance)
         hit_off, hits = eng.fetch_hits()
