@@ -201,6 +201,12 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   store; no qualities for one that masks       min_qual > 0: MNC_ERR_ARG; after a call of both passes: MNC_ERR_UNSUPPORTED
  *   a reference base with 2^31 or more           outside the contract: every plane of mnc_pileup holds int32 per base
  *   observations in one pileup plane             (mnc_pileup_reset starts over)
+ *   linkage after a call that ran both the       mnc_engine_add_linkage: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
+ *   usual and the wide pass                      coverage); a call whose reads are all long adds like any other
+ *   linkage under MNC_CONTRACT_CHAIN             mnc_engine_add_linkage: MNC_ERR_ARG (no CIGAR to take the columns from)
+ *   a linkage window outside 1 .. 64, more than  mnc_linkage_create: MNC_ERR_ARG (a lane looks back over the 64 sites in front
+ *   2^30 sites, a '+' site, an unsorted list     of its own; insertion alleles are not linked)
+ *   2^31 or more records at one site or pair     outside the contract: every word of mnc_linkage holds int32
  *   abundance after a call that ran both the     mnc_engine_add_abundance: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
  *   usual and the wide pass                      coverage); a call whose reads are all long adds like any other
  *   abundance under MNC_CONTRACT_CHAIN           mnc_engine_add_abundance: MNC_ERR_ARG (no dp_max to compare the genomes by)
@@ -707,6 +713,70 @@ int  mnc_pileup_call_variants_strands(mnc_pileup *pu, int rid, int32_t min_depth
 /* The raw additive planes of the store (device pointers; any may be NULL), for a collective of the caller's, as
  * mnc_pileup_device hands out the others: 10 * n_words more words.  MNC_ERR_ARG without a strand store. */
 int  mnc_pileup_strands_device(mnc_pileup *pu, const int32_t **d_track_fwd, const int32_t **d_alt_fwd, const int32_t **d_lowq);
+
+/* ---------------------------------------------------------------- linkage
+ * Which variant alleles the reads carry TOGETHER.  mnc_pileup_call_variants says that a base is 60 % A and 40 % G; it cannot
+ * say that the G here travels with the T 300 bases further on -- and a 5 kb read crosses many variant sites at once.  That
+ * pairing separates two strains of one species from one strain with sequencing noise.  An mnc_linkage is the fifth
+ * accumulator beside the engine and has mnc_pileup's lifetime, threading and cost rules: one index, one device, added to from
+ * the last batch as it stands in HBM on the engine's stream with no host wait (csrc/k_linkage.hip); engines of the same index
+ * and device may add from their own threads; reset and the read-outs are for one thread at a time; a batch that does not ask
+ * costs not one more kernel, allocation or byte.  Integer arithmetic throughout.
+ *
+ * Sites.  At creation the caller hands over n_sites records of mnc_variant_t, as mnc_pileup_call_variants writes them;
+ * `span`, `count` and `ref` are ignored (the reference base is the index's).  They must ascend strictly in (rid, pos, allele
+ * order A C G T -), so two alleles of one position are two sites; `alt` is one of 'A' 'C' 'G' 'T' '-'.  The list is copied
+ * to the device and fixed for the accumulator's life, as is the window W (1 .. MNC_LINKAGE_MAX_WINDOW).
+ *
+ * What one record says at site s of its own contig (records selected by `what` exactly as mnc_engine_add_pileup selects;
+ * query columns on the hit's strand, as there):
+ *   ALT      `alt` is a base: the column over pos is an M column whose read base equals it;  `alt` is '-': a D column
+ *   REF      otherwise, the column is an M column, the reference base is not N and the read base equals it
+ *   nothing  otherwise: not covered (pos outside [rs, re)), another allele, an N
+ * What is accumulated, all int32:
+ *   site[n_sites][2]      the REF and the ALT statements per site
+ *   pair[n_sites][W][4]   for site i and d = 0 .. W - 1, j = i + d + 1 on the same contig: cell 2 * a_i + a_j (REF = 0,
+ *                         ALT = 1) counts the RECORDS that made a statement at both sites (two records of one read are two
+ *                         records).  Slots whose j is past the contig's last site stay zero.
+ * Addition commutes: the result does not depend on order or on how a sample was cut into batches.
+ *
+ * Storage (what mnc_linkage_device hands out): d_site is site[][] as above.  d_pair is 5 * n_sites * W words: first
+ * [n_sites][W][4] = {missing, n01, n10, n11}, then a difference track[n_sites][W].  Per record and d the pairs (i, j) inside
+ * the record's range of sites are a run of i: +1 at its first i, -1 one past its last.  A pair inside the range costs one
+ * atomic only where it is not REF / REF -- `missing` where either site has no statement -- and
+ *   n00[i][d] = (track[0][d] + .. + track[i][d]) - (missing + n01 + n10 + n11)[i][d]
+ * Every word is additive, the differences included: ranks sum them with one collective of their own. */
+typedef struct mnc_linkage mnc_linkage;
+#define MNC_LINKAGE_MAX_WINDOW 64
+#define MNC_LINKAGE_MAX_SITES  ((int64_t)1 << 30)
+/* MNC_ERR_ARG, before any device is looked at: a NULL pointer; window outside 1 .. 64; n_sites negative or above
+ * MNC_LINKAGE_MAX_SITES; a site outside the index; an `alt` that is none of A C G T - (a '+' record: the message names the
+ * record -- insertion alleles are not linked); a list that does not ascend strictly.  MNC_ERR_NODEVICE without a gfx950
+ * device, MNC_ERR_NOMEM when 20 * W + 50 bytes per site do not fit the HBM that is free. */
+int  mnc_linkage_create(mnc_index *idx, int device, const mnc_variant_t *sites, int64_t n_sites, int32_t window, mnc_linkage **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_linkage_free(mnc_linkage *lk);
+/* clears every word (the site list stays); asynchronous */
+int  mnc_linkage_reset(mnc_linkage *lk);
+/* HBM the accumulator holds: 20 * W + 8 bytes per site of words, 9 of the list, 33 of the phase read-out's scratch */
+int  mnc_linkage_device_bytes(const mnc_linkage *lk, int64_t *bytes);
+/* Adds the last classified batch of `eng`; answers as mnc_engine_add_pileup answers in the same situations (another index or
+ * device, the selector, no batch, MNC_CONTRACT_CHAIN: MNC_ERR_ARG; a call of both passes: MNC_ERR_UNSUPPORTED), the
+ * accumulator untouched on any error.  Asynchronous on the engine's stream, no host wait. */
+int  mnc_engine_add_linkage(mnc_engine *eng, mnc_linkage *lk, int what);
+/* Rows [first, first + n) of site[][] / of pair[][][] with n00 derived (MNC_ERR_ARG outside the list).  Wait for the work
+ * queued so far and leave the accumulator as it is, like mnc_linkage_phase. */
+int  mnc_linkage_fetch_sites(mnc_linkage *lk, int64_t first, int64_t n, int32_t *out /* [n][2] */);
+int  mnc_linkage_fetch_pairs(mnc_linkage *lk, int64_t first, int64_t n, int32_t *out /* [n][window][4] */);
+/* Phase blocks from the ADJACENT pairs (d = 0), on the device -- count, scan, write -- so only the answer travels.  For site
+ * i >= 1 on the contig of site i - 1: cis = n00 + n11, trans = n01 + n10, tot = cis + trans; site i is linked to i - 1 iff
+ * tot >= min_pairs, cis != trans and |cis - trans| * 1000 >= min_permille * tot (int64).  A site that is not linked, and
+ * every contig's first site, starts a block.  block[i] = the block starts before or at i, minus one; phase[i] = 0 at a block
+ * start, else phase[i - 1] XOR (trans > cis). */
+int  mnc_linkage_phase(mnc_linkage *lk, int32_t min_pairs, int32_t min_permille, int32_t *block /* [n_sites] */, uint8_t *phase /* [n_sites] */);
+/* The raw additive words (device pointers, laid out as above; either may be NULL), for a collective of the caller's.  Ordered
+ * behind the adds only after a read-out call or a sync of the engines that added. */
+int  mnc_linkage_device(mnc_linkage *lk, const int32_t **d_site, const int32_t **d_pair);
 
 /* ---------------------------------------------------------------- abundance
  * Which of several close genomes is in the sample, and how much of each: the other half of the focus pass' question.  The

@@ -98,6 +98,8 @@ EXPORTS = [
     "mnc_pileup_fetch_counts", "mnc_pileup_call_variants", "mnc_pileup_consensus",
     "mnc_pileup_store_insertions", "mnc_pileup_add_insertion_list", "mnc_pileup_insertion_info", "mnc_pileup_call_insertions", "mnc_pileup_consensus_ins",
     "mnc_pileup_store_strands", "mnc_engine_add_pileup_quals", "mnc_pileup_fetch_strand_counts", "mnc_pileup_call_variants_strands", "mnc_pileup_strands_device",
+    "mnc_linkage_create", "mnc_linkage_free", "mnc_linkage_reset", "mnc_linkage_device_bytes", "mnc_engine_add_linkage",
+    "mnc_linkage_fetch_sites", "mnc_linkage_fetch_pairs", "mnc_linkage_phase", "mnc_linkage_device",
     "mnc_abundance_create", "mnc_abundance_free", "mnc_abundance_reset", "mnc_abundance_device_bytes", "mnc_engine_add_abundance",
     "mnc_abundance_add_lists", "mnc_abundance_info", "mnc_abundance_fetch_unique", "mnc_abundance_fetch_lists", "mnc_abundance_solve",
     "mnc_abundance_device", "mnc_abundance_create_global", "mnc_abundance_add_carry",
@@ -262,6 +264,15 @@ def lib():
     sig("mnc_pileup_fetch_strand_counts", i32, [vp, i32, i64, i64, vp])
     sig("mnc_pileup_call_variants_strands", i32, [vp, i32, i32, i32, i32, i32, i32, vp, i64, C.POINTER(i64)])
     sig("mnc_pileup_strands_device", i32, [vp, pp, pp, pp])
+    sig("mnc_linkage_create", i32, [vp, i32, vp, i64, i32, pp])
+    sig("mnc_linkage_free", None, [vp])
+    sig("mnc_linkage_reset", i32, [vp])
+    sig("mnc_linkage_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_engine_add_linkage", i32, [vp, vp, i32])
+    sig("mnc_linkage_fetch_sites", i32, [vp, i64, i64, vp])
+    sig("mnc_linkage_fetch_pairs", i32, [vp, i64, i64, vp])
+    sig("mnc_linkage_phase", i32, [vp, i32, i32, vp, vp])
+    sig("mnc_linkage_device", i32, [vp, pp, pp])
     sig("mnc_abundance_create", i32, [vp, i32, i64, C.c_int32, C.c_int32, pp])
     sig("mnc_abundance_free", None, [vp])
     sig("mnc_abundance_reset", i32, [vp])
@@ -633,6 +644,11 @@ class Engine:
             quals = quals.ctypes.data if quals.size else None
         self._add("mnc_engine_add_pileup_quals", pileup, int(what), quals, 1 if quals_on_device else 0)
 
+    def add_linkage(self, linkage, what=COV_GATED):
+        """`mnc_engine_add_linkage`: add the last classified batch, as it stands in HBM, to the accumulator `linkage`.
+        `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
+        self._add("mnc_engine_add_linkage", linkage, int(what))
+
     def add_abundance(self, abundance):
         """`mnc_engine_add_abundance`: add the candidate genomes of every read of the last classified batch, as it stands in
         HBM, to the accumulator `abundance`.  Asynchronous."""
@@ -924,6 +940,52 @@ class Pileup(_Accumulator):
         d, a, n = C.c_void_p(), C.c_void_p(), C.c_int64(0)
         check(lib().mnc_pileup_device(self._h, C.byref(d), C.byref(a), C.byref(n)))
         return int(d.value or 0), int(a.value or 0), int(n.value)
+
+
+# ---------------------------------------------------------------------------------- linkage
+LINKAGE_MAX_WINDOW = 64
+
+
+class Linkage(_Accumulator):
+    """Owner of an ``mnc_linkage``: per site of a fixed list (`sites`: a VARIANT_DTYPE array in (rid, pos, allele) order,
+    as `Pileup.variants` returns it, without '+' rows) how many records say REF and ALT, and per pair of sites up to
+    `window` apart in the list the four joint counts -- accumulated from batch to batch by `Engine.add_linkage`
+    (include/monica_amd.h, "linkage").  `phase()` turns the adjacent pairs into phase blocks on the device."""
+
+    _c = "linkage"
+
+    def __init__(self, index, sites, window=16, device=0):
+        self.index = index
+        self.sites = np.ascontiguousarray(sites, dtype=VARIANT_DTYPE)
+        self.window = int(window)
+        self._create(index, device, self.sites.ctypes.data if len(self.sites) else None, len(self.sites), self.window)
+
+    def site_counts(self, first=0, n=None):
+        """int32[n, 2]: the REF and the ALT statements of sites [first, first + n) (to the end by default)."""
+        n = len(self.sites) - int(first) if n is None else int(n)
+        out = np.zeros((max(n, 0), 2), dtype=np.int32)
+        check(lib().mnc_linkage_fetch_sites(self._h, int(first), n, out.ctypes.data if out.size else None))
+        return out
+
+    def pairs(self, first=0, n=None):
+        """int32[n, window, 4]: cell 2 * a_i + a_j (REF 0, ALT 1) of site i = first + row and site j = i + d + 1."""
+        n = len(self.sites) - int(first) if n is None else int(n)
+        out = np.zeros((max(n, 0), self.window, 4), dtype=np.int32)
+        check(lib().mnc_linkage_fetch_pairs(self._h, int(first), n, out.ctypes.data if out.size else None))
+        return out
+
+    def phase(self, min_pairs=1, min_permille=0):
+        """`mnc_linkage_phase`: (block int32[n_sites], phase uint8[n_sites]) from the adjacent pairs."""
+        block, phase = np.zeros(len(self.sites), dtype=np.int32), np.zeros(len(self.sites), dtype=np.uint8)
+        check(lib().mnc_linkage_phase(self._h, int(min_pairs), int(min_permille), block.ctypes.data if len(block) else None,
+                                      phase.ctypes.data if len(phase) else None))
+        return block, phase
+
+    def device(self):
+        """(device address of site[n_sites][2], of the 5 * n_sites * window raw pair words): `mnc_linkage_device`."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().mnc_linkage_device(self._h, C.byref(a), C.byref(b)))
+        return int(a.value or 0), int(b.value or 0)
 
 
 # ---------------------------------------------------------------------------------- abundance

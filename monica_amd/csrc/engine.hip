@@ -106,6 +106,8 @@ int pileup_add(mnc_pileup *pu, const Batch &B, int sel, hipStream_t st, const ui
 int pileup_quals_check(const mnc_pileup *pu, bool with_quals);   // k_pile_strand.hip
 int pileup_min_qual(const mnc_pileup *pu);
 int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st);
+const Accum *as_accum(const mnc_linkage *lk);               // k_linkage.hip
+int linkage_add(mnc_linkage *lk, const Batch &B, int sel, hipStream_t st);
 // the candidate carry (k_carry.hip): an Accum of a device, of no index
 const Accum *as_accum(const mnc_carry *cc);
 int carry_add(mnc_carry *cc, const Batch &B, int n_contigs, int n_genomes, int64_t first_read, int32_t genome_offset, hipStream_t st);
@@ -1786,6 +1788,19 @@ extern "C" int mnc_engine_add_pileup(mnc_engine *e, mnc_pileup *pu, int what)
 	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
 	return pileup_add(pu, e->B, sel, e->stream, nullptr);
+}
+
+// ---------------------------------------------------------------- linkage of the last batch
+// The same for the pair tables of a site list (k_linkage.hip): the pileup's checks, one kernel on the engine's stream.
+extern "C" int mnc_engine_add_linkage(mnc_engine *e, mnc_linkage *lk, int what)
+{
+	if (!e || !lk) return MNC_ERR_ARG;
+	int sel = 0;
+	if (int rc = add_selector(what, true, &sel)) return rc;
+	if (int rc = add_precheck(e, as_accum(lk), "linkage", "linkage needs the CIGARs of MNC_CONTRACT_DP")) return rc;
+	if (e->B.n_reads == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return linkage_add(lk, e->B, sel, e->stream);
 }
 
 // ... with the batch's quality characters, for a pileup with the strand store (k_pile_strand.hip).  A host array goes to a

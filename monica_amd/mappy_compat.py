@@ -338,6 +338,11 @@ class Aligner:
         forward records' counts apart and masks M columns below that base quality (`map_batch(quals=)`)."""
         return _capi.Pileup(self._index, self._device, insertions=insertions, strands=strands)
 
+    def linkage(self, sites, window=16):
+        """A linkage accumulator (`_capi.Linkage`) over `sites` (rows of `Pileup.variants`, without '+' alleles) for this
+        index on this object's device: pass it to `map_batch` in a second pass over the reads, then `phase()` it."""
+        return _capi.Linkage(self._index, sites, window, self._device)
+
     def abundance(self, cap_cands=_capi.ABUNDANCE_CAP_CANDS, max_delta=_capi.ABUNDANCE_MAX_DELTA, scale_q=_capi.ABUNDANCE_SCALE_Q):
         """An abundance accumulator (`_capi.Abundance`) for this index on this object's device: pass it to `map_batch`,
         then `solve()` it."""
@@ -353,14 +358,15 @@ class Aligner:
         return _capi.Abundance.global_(self._device, len(genome_names), cap_cands, max_delta, scale_q, genome_names=genome_names)
 
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
-                  abundance=None, quals=None):
+                  abundance=None, quals=None, linkage=None, linkage_what=_capi.COV_GATED):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
         added to it -- `coverage_what`: one `_capi.COV_*` selector, optionally | COV_SPAN -- before the hits are fetched; with
         `pileup` (an accumulator of `pileup()`) likewise, `pileup_what` one selector; with `abundance` (an accumulator of
         `abundance()`) every read's candidate genomes are added to it.  `quals`: the batch's Phred+33 characters at
-        `offsets`, for a `pileup(strands=min_qual)` that masks by base quality."""
+        `offsets`, for a `pileup(strands=min_qual)` that masks by base quality.  With `linkage` (an accumulator of
+        `linkage()`) the batch is added to it, `linkage_what` one selector."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -375,6 +381,8 @@ class Aligner:
             eng.add_pileup(pileup, pileup_what, quals=quals)
         if abundance is not None:
             eng.add_abundance(abundance)
+        if linkage is not None:
+            eng.add_linkage(linkage, linkage_what)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
