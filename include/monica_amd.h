@@ -207,6 +207,17 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   a linkage window outside 1 .. 64, more than  mnc_linkage_create: MNC_ERR_ARG (a lane looks back over the 64 sites in front
  *   2^30 sites, a '+' site, an unsorted list     of its own; insertion alleles are not linked)
  *   2^31 or more records at one site or pair     outside the contract: every word of mnc_linkage holds int32
+ *   haplotags after a call that ran both the     mnc_engine_add_haplotag: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
+ *   usual and the wide pass; under               linkage); MNC_ERR_ARG under MNC_CONTRACT_CHAIN (no CIGAR to take the columns
+ *   MNC_CONTRACT_CHAIN                           from)
+ *   a batch of more reads than cap_reads         mnc_engine_add_haplotag: MNC_ERR_RANGE, the accumulator untouched (the tag
+ *                                                buffer is allocated once, at creation)
+ *   a '+' site, an unsorted list; block[] /      mnc_haplotag_create: MNC_ERR_ARG (insertion alleles cast no vote; blocks are
+ *   phase[] not as mnc_linkage_phase writes them runs of the list, a contig's first site starts one at phase 0)
+ *   tags of an earlier add, or of two engines    not kept: tag[] and votes[] are the most recent add's (one mnc_haplotag per
+ *   adding to one mnc_haplotag                   engine; the block tables sum)
+ *   2^31 or more records or minority votes in    outside the contract: every word of mnc_haplotag holds int32
+ *   one block
  *   abundance after a call that ran both the     mnc_engine_add_abundance: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
  *   usual and the wide pass                      coverage); a call whose reads are all long adds like any other
  *   abundance under MNC_CONTRACT_CHAIN           mnc_engine_add_abundance: MNC_ERR_ARG (no dp_max to compare the genomes by)
@@ -777,6 +788,65 @@ int  mnc_linkage_phase(mnc_linkage *lk, int32_t min_pairs, int32_t min_permille,
 /* The raw additive words (device pointers, laid out as above; either may be NULL), for a collective of the caller's.  Ordered
  * behind the adds only after a read-out call or a sync of the engines that added. */
 int  mnc_linkage_device(mnc_linkage *lk, const int32_t **d_site, const int32_t **d_pair);
+
+/* ---------------------------------------------------------------- haplotag
+ * Which READS belong to which side of a phase block, and how many.  mnc_linkage_phase ends at block[] / phase[]: it says
+ * which alleles travel together, not which reads carry them, how many reads stand behind each side of a block or in what
+ * ratio two strains are present.  An mnc_haplotag is the sixth accumulator beside the engine and has mnc_linkage's lifetime,
+ * threading and cost rules (one index, one device; added to from the last batch as it stands in HBM on the engine's stream
+ * with no host wait, csrc/k_haplotag.hip; engines of the same index and device may add from their own threads; reset and
+ * the read-outs are for one thread at a time; a batch that does not ask costs nothing).  Integer arithmetic throughout.
+ *
+ * Creation takes the site list mnc_linkage_create takes, under the same checks, and per site block[] (int32) and phase[]
+ * (uint8) as mnc_linkage_phase writes them -- from that call, or merged elsewhere by the caller.  They are copied to the
+ * device and fixed for the accumulator's life, as are the two thresholds and cap_reads, the most reads a batch may hold.
+ *
+ * Votes.  What one selected record says at a site is the linkage section's REF / ALT / nothing rule, word for word.  A
+ * statement a (REF = 0, ALT = 1) at site i is one vote for haplotype a XOR phase[i] of block block[i].
+ * Decision, per (selected record, block in which it made at least one statement): n0 and n1 its votes, tot = n0 + n1; the
+ * record is DECIDED for the larger side iff tot >= min_votes, n0 != n1 and |n0 - n1| * 1000 >= min_permille * tot (int64),
+ * UNDECIDED otherwise.  A block in which the record said nothing is not touched.
+ * What is accumulated, int32:
+ *   blk[n_blocks][4]   records decided for haplotype 0, for haplotype 1, undecided records, and the minority votes
+ *                      min(n0, n1) summed over all those records (what contradicts a record's own majority: noise, or a
+ *                      wrong phase).  n_blocks = block[n_sites - 1] + 1.
+ * Addition commutes: the table does not depend on order or on how a sample was cut into batches.
+ * Per read r of the MOST RECENT add, not accumulated: among the read's decided (record, block) pairs -- ordered by record as
+ * the add walks a read's records (region-list order), then by ascending block -- the one with the largest |n0 - n1|, ties to
+ * the first:
+ *   tag[r] = block * 2 + haplotype,  votes[r] = {the winner's votes, the loser's}
+ *   tag[r] = -1, votes[r] = {0, 0}   no decided pair: no record, no site under one, a read of no bases
+ * The tags belong to the latest add, whichever engine made it: with several engines use one mnc_haplotag per engine and sum
+ * the block tables (mnc_haplotag_device: every word of blk is additive). */
+typedef struct mnc_haplotag mnc_haplotag;
+#define MNC_HAPLOTAG_MAX_READS ((int64_t)1 << 30)
+/* MNC_ERR_ARG, before any device is looked at: whatever mnc_linkage_create refuses in a site list, with its messages (a '+'
+ * record is named); then, the message naming the site: block[0] != 0; block[i] - block[i - 1] neither 0 nor 1; a contig's
+ * first site that does not start a block; a phase[i] that is neither 0 nor 1, or 1 at a block's first site; then
+ * min_votes < 1, min_permille outside 0 .. 1000, cap_reads outside 1 .. MNC_HAPLOTAG_MAX_READS.  MNC_ERR_NODEVICE without a
+ * gfx950 device, MNC_ERR_NOMEM when the HBM that is free does not hold it. */
+int  mnc_haplotag_create(mnc_index *idx, int device, const mnc_variant_t *sites, int64_t n_sites, const int32_t *block /* [n_sites] */,
+                         const uint8_t *phase /* [n_sites] */, int64_t cap_reads, int32_t min_votes, int32_t min_permille, mnc_haplotag **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_haplotag_free(mnc_haplotag *ht);
+/* clears blk, sets every tag to -1 and every votes pair to {0, 0} (lists and thresholds stay); asynchronous */
+int  mnc_haplotag_reset(mnc_haplotag *ht);
+/* HBM the accumulator holds: 10 bytes per site, 16 per block, 12 per read of cap_reads */
+int  mnc_haplotag_device_bytes(const mnc_haplotag *ht, int64_t *bytes);
+int  mnc_haplotag_n_blocks(const mnc_haplotag *ht, int64_t *n_blocks);
+/* Adds the last classified batch of `eng` and writes its reads' tags; the selectors, refusals and return codes of
+ * mnc_engine_add_linkage, and MNC_ERR_RANGE when the batch holds more than cap_reads reads; the accumulator untouched on any
+ * error.  Asynchronous on the engine's stream, no host wait. */
+int  mnc_engine_add_haplotag(mnc_engine *eng, mnc_haplotag *ht, int what);
+/* Rows [first, first + n) of blk (MNC_ERR_ARG outside the table).  Waits for the work queued so far and leaves the
+ * accumulator as it is, like mnc_haplotag_fetch_tags. */
+int  mnc_haplotag_fetch_blocks(mnc_haplotag *ht, int64_t first, int64_t n, int32_t *out /* [n][4] */);
+/* The tags of the most recent add; either pointer may be NULL.  n_reads must be that add's read count (0 before the first
+ * add): MNC_ERR_ARG otherwise. */
+int  mnc_haplotag_fetch_tags(mnc_haplotag *ht, int64_t n_reads, int32_t *tag /* [n_reads] */, int32_t *votes /* [n_reads][2] */);
+/* The raw additive blk words and the tag buffer (tag[cap_reads], then votes[cap_reads][2]) as device pointers; either may
+ * be NULL.  Ordered behind the adds only after a read-out call or a sync of the engines that added. */
+int  mnc_haplotag_device(mnc_haplotag *ht, const int32_t **d_blk, const int32_t **d_tag);
 
 /* ---------------------------------------------------------------- abundance
  * Which of several close genomes is in the sample, and how much of each: the other half of the focus pass' question.  The

@@ -100,6 +100,8 @@ EXPORTS = [
     "mnc_pileup_store_strands", "mnc_engine_add_pileup_quals", "mnc_pileup_fetch_strand_counts", "mnc_pileup_call_variants_strands", "mnc_pileup_strands_device",
     "mnc_linkage_create", "mnc_linkage_free", "mnc_linkage_reset", "mnc_linkage_device_bytes", "mnc_engine_add_linkage",
     "mnc_linkage_fetch_sites", "mnc_linkage_fetch_pairs", "mnc_linkage_phase", "mnc_linkage_device",
+    "mnc_haplotag_create", "mnc_haplotag_free", "mnc_haplotag_reset", "mnc_haplotag_device_bytes", "mnc_haplotag_n_blocks",
+    "mnc_engine_add_haplotag", "mnc_haplotag_fetch_blocks", "mnc_haplotag_fetch_tags", "mnc_haplotag_device",
     "mnc_abundance_create", "mnc_abundance_free", "mnc_abundance_reset", "mnc_abundance_device_bytes", "mnc_engine_add_abundance",
     "mnc_abundance_add_lists", "mnc_abundance_info", "mnc_abundance_fetch_unique", "mnc_abundance_fetch_lists", "mnc_abundance_solve",
     "mnc_abundance_device", "mnc_abundance_create_global", "mnc_abundance_add_carry",
@@ -273,6 +275,15 @@ def lib():
     sig("mnc_linkage_fetch_pairs", i32, [vp, i64, i64, vp])
     sig("mnc_linkage_phase", i32, [vp, i32, i32, vp, vp])
     sig("mnc_linkage_device", i32, [vp, pp, pp])
+    sig("mnc_haplotag_create", i32, [vp, i32, vp, i64, vp, vp, i64, i32, i32, pp])
+    sig("mnc_haplotag_free", None, [vp])
+    sig("mnc_haplotag_reset", i32, [vp])
+    sig("mnc_haplotag_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_haplotag_n_blocks", i32, [vp, C.POINTER(i64)])
+    sig("mnc_engine_add_haplotag", i32, [vp, vp, i32])
+    sig("mnc_haplotag_fetch_blocks", i32, [vp, i64, i64, vp])
+    sig("mnc_haplotag_fetch_tags", i32, [vp, i64, vp, vp])
+    sig("mnc_haplotag_device", i32, [vp, pp, pp])
     sig("mnc_abundance_create", i32, [vp, i32, i64, C.c_int32, C.c_int32, pp])
     sig("mnc_abundance_free", None, [vp])
     sig("mnc_abundance_reset", i32, [vp])
@@ -649,6 +660,12 @@ class Engine:
         `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
         self._add("mnc_engine_add_linkage", linkage, int(what))
 
+    def add_haplotag(self, haplotag, what=COV_GATED):
+        """`mnc_engine_add_haplotag`: add the last classified batch, as it stands in HBM, to the accumulator `haplotag` and
+        write its reads' tags.  `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
+        self._add("mnc_engine_add_haplotag", haplotag, int(what))
+        haplotag.n_reads = self.n_reads
+
     def add_abundance(self, abundance):
         """`mnc_engine_add_abundance`: add the candidate genomes of every read of the last classified batch, as it stands in
         HBM, to the accumulator `abundance`.  Asynchronous."""
@@ -985,6 +1002,54 @@ class Linkage(_Accumulator):
         """(device address of site[n_sites][2], of the 5 * n_sites * window raw pair words): `mnc_linkage_device`."""
         a, b = C.c_void_p(), C.c_void_p()
         check(lib().mnc_linkage_device(self._h, C.byref(a), C.byref(b)))
+        return int(a.value or 0), int(b.value or 0)
+
+
+# ---------------------------------------------------------------------------------- haplotag
+class Haplotag(_Accumulator):
+    """Owner of an ``mnc_haplotag``: per phase block of a site list (`sites` as `Linkage` takes them, `block` / `phase` as
+    `Linkage.phase` returns them) how many records were decided for haplotype 0, for haplotype 1, stayed undecided, and their
+    minority votes -- accumulated from batch to batch by `Engine.add_haplotag` -- and per read of the latest add its tag
+    (include/monica_amd.h, "haplotag").  `cap_reads`: the most reads a batch may hold."""
+
+    _c = "haplotag"
+
+    def __init__(self, index, sites, block, phase, cap_reads, min_votes=2, min_permille=600, device=0):
+        self.index = index
+        self.sites = np.ascontiguousarray(sites, dtype=VARIANT_DTYPE)
+        block, phase = np.ascontiguousarray(block, dtype=np.int32), np.ascontiguousarray(phase, dtype=np.uint8)
+        if not len(block) == len(phase) == len(self.sites):
+            raise ValueError("block and phase hold one entry per site")
+        self.n_reads = 0                                        # of the latest add (Engine.add_haplotag)
+        n = len(self.sites)
+        self._create(index, device, self.sites.ctypes.data if n else None, n, block.ctypes.data if n else None, phase.ctypes.data if n else None,
+                     int(cap_reads), int(min_votes), int(min_permille))
+
+    @property
+    def n_blocks(self):
+        n = C.c_int64(0)
+        check(lib().mnc_haplotag_n_blocks(self._h, C.byref(n)))
+        return int(n.value)
+
+    def blocks(self, first=0, n=None):
+        """int32[n, 4]: records decided for haplotype 0, for haplotype 1, undecided, minority votes -- of blocks
+        [first, first + n) (to the end by default)."""
+        n = self.n_blocks - int(first) if n is None else int(n)
+        out = np.zeros((max(n, 0), 4), dtype=np.int32)
+        check(lib().mnc_haplotag_fetch_blocks(self._h, int(first), n, out.ctypes.data if out.size else None))
+        return out
+
+    def tags(self):
+        """(tag int32[n_reads], votes int32[n_reads, 2]) of the latest add: block * 2 + haplotype and {winner's, loser's}
+        votes; -1 and {0, 0} for a read without a decision."""
+        tag, votes = np.zeros(self.n_reads, dtype=np.int32), np.zeros((self.n_reads, 2), dtype=np.int32)
+        check(lib().mnc_haplotag_fetch_tags(self._h, self.n_reads, tag.ctypes.data if tag.size else None, votes.ctypes.data if tag.size else None))
+        return tag, votes
+
+    def device(self):
+        """(device address of blk[n_blocks][4], of tag[cap_reads] with votes[cap_reads][2] behind it): `mnc_haplotag_device`."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().mnc_haplotag_device(self._h, C.byref(a), C.byref(b)))
         return int(a.value or 0), int(b.value or 0)
 
 

@@ -108,6 +108,9 @@ int pileup_min_qual(const mnc_pileup *pu);
 int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st);
 const Accum *as_accum(const mnc_linkage *lk);               // k_linkage.hip
 int linkage_add(mnc_linkage *lk, const Batch &B, int sel, hipStream_t st);
+const Accum *as_accum(const mnc_haplotag *ht);              // k_haplotag.hip
+int haplotag_fits(const mnc_haplotag *ht, const Batch &B);
+int haplotag_add(mnc_haplotag *ht, const Batch &B, int sel, hipStream_t st);
 // the candidate carry (k_carry.hip): an Accum of a device, of no index
 const Accum *as_accum(const mnc_carry *cc);
 int carry_add(mnc_carry *cc, const Batch &B, int n_contigs, int n_genomes, int64_t first_read, int32_t genome_offset, hipStream_t st);
@@ -1801,6 +1804,20 @@ extern "C" int mnc_engine_add_linkage(mnc_engine *e, mnc_linkage *lk, int what)
 	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
 	return linkage_add(lk, e->B, sel, e->stream);
+}
+
+// ---------------------------------------------------------------- haplotags of the last batch
+// The same for the votes per phase block (k_haplotag.hip): linkage's checks, then the tag buffer's capacity; one kernel on the
+// engine's stream.  An empty batch is an add of no reads: the tags are the last add's.
+extern "C" int mnc_engine_add_haplotag(mnc_engine *e, mnc_haplotag *ht, int what)
+{
+	if (!e || !ht) return MNC_ERR_ARG;
+	int sel = 0;
+	if (int rc = add_selector(what, true, &sel)) return rc;
+	if (int rc = add_precheck(e, as_accum(ht), "haplotags", "haplotags need the CIGARs of MNC_CONTRACT_DP")) return rc;
+	if (int rc = haplotag_fits(ht, e->B)) return rc;
+	HIP_TRY(hipSetDevice(e->device));
+	return haplotag_add(ht, e->B, sel, e->stream);
 }
 
 // ... with the batch's quality characters, for a pileup with the strand store (k_pile_strand.hip).  A host array goes to a

@@ -31,20 +31,15 @@
 #include <hip/hip_runtime.h>
 #include <new>
 #include <vector>
-#include "pileup.h"
+#include "linkage.h"
 
 using namespace mnc;
-
-// a site's allele is held as the pileup numbers its channels (pileup.h): 0 .. 3 = A C G T, CH_DEL = deleted
 
 struct mnc_linkage : mnc::Accum {
 	int64_t n_sites = 0;
 	int window = 0, n_contigs = 0;
-	int32_t *d_pos = nullptr;                  // [n_sites] the sites' positions ...
-	int32_t *d_rid = nullptr;                  // ... contigs ...
-	uint8_t *d_alt = nullptr;                  // ... and alleles
-	int32_t *d_first = nullptr;                // [n_contigs + 1] the first site of every contig
-	int64_t *d_off = nullptr;                  // [n_contigs + 1] the contigs' first bases in the 4-bit store
+	LinkSitesDev list;                         // the sites' positions and alleles, the contigs' first sites and first bases (linkage.h)
+	int32_t *d_rid = nullptr;                  // [n_sites] the sites' contigs
 	int32_t *site = nullptr;                   // [n_sites][2]
 	int32_t *pair = nullptr;                   // [n_sites][window][4]: missing, n01, n10, n11; behind them track[n_sites][window]
 	int32_t *track = nullptr;
@@ -59,116 +54,45 @@ struct mnc_linkage : mnc::Accum {
 namespace mnc {
 
 struct LinkView {
-	const int32_t *pos, *first;
-	const uint8_t *alt;
-	const int64_t *off;
-	int n_contigs, window;
+	LinkSites list;
+	int window;
 	int32_t *site, *pair, *track;
 };
 
-__device__ __forceinline__ void link_put(int32_t *w, int v) { (void)__hip_atomic_fetch_add(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the first site of [lo, hi) whose position is not below p (the same answer in every lane)
-__device__ __forceinline__ int link_lower(const int32_t *pos, int lo, int hi, int p)
-{
-	while (lo < hi) {
-		const int mid = lo + (hi - lo) / 2;
-		if (pos[mid] < p) lo = mid + 1; else hi = mid;
-	}
-	return lo;
-}
-
+// the walk is linkage.h's; here, what is done with the 64 statements it hands over
 __global__ __launch_bounds__(256) void mnc_link_add(Batch B, int sel, LinkView L)
 {
 	const int lane = lane_id(), W = L.window;
 	const uint32_t rd = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
 	if (rd >= B.n_reads) return;                              // (whole waves; the kernel has no workgroup barrier)
-	const int64_t read_off = B.offsets[rd];
-	const int qlen = (int)(B.offsets[rd + 1] - read_off);
-	if (qlen <= 0) return;
-	const uint8_t *read = B.bases + read_off;
-	cov_for_records(B, rd, sel, L.n_contigs, [&](const mnc_reg_t &r, int64_t slot) {
-		const int n_c = r.n_cigar;
-		if (n_c <= 0) return;
-		const int s_lo = link_lower(L.pos, L.first[r.rid], L.first[r.rid + 1], r.rs);
-		const int s_hi = link_lower(L.pos, s_lo, L.first[r.rid + 1], r.re);
-		if (s_lo >= s_hi) return;                               // no site under this record
-		const int64_t coff = L.off[r.rid];
-		const uint32_t *src = B.cig_reg + B.regdp[slot].cig_off;
-		auto Q = [&](int p) -> int {                            // column p of the query side, on the hit's strand (pile_add_read)
-			int at = r.rev ? r.qe - 1 - p : r.qs + p;
-			at = at < 0 ? 0 : at >= qlen ? qlen - 1 : at;
-			const int c = base_nt4(read[at]);
-			return r.rev ? (c < 4 ? 3 - c : 4) : c;
-		};
+	int s_lo = 0;
+	unsigned long long p_ref = 0, p_alt = 0;                  // the statements of the 64 sites before
+	link_walk(B, rd, sel, L.list, [&](int lo, int s_hi) {
+		s_lo = lo, p_ref = p_alt = 0;
 		// ---- the pairs inside the record's range, per distance: lane d's run of i is [s_lo, s_hi - d - 1)
 		if (lane < W && s_hi - lane - 1 > s_lo) {
 			link_put(L.track + (int64_t)s_lo * W + lane, 1);
 			link_put(L.track + (int64_t)(s_hi - lane - 1) * W + lane, -1);
 		}
-		// ---- the chunk of 64 operations at hand
-		int k0 = 0, qoff = 0;                                   // its first operation; query columns before it
-		int64_t toff = r.rs;                                    // reference position before it
-		int op = 0, it = 0, my_t0 = 0, my_q0 = 0, tot_t = 0, tot_q = 0;
-		auto load = [&] {
-			const int k = k0 + lane;
-			const uint32_t wd = k < n_c ? src[k] : 0u;
-			op = (int)(wd & 0xfu);
-			const int l = k < n_c && op <= 2 ? (int)(wd >> 4) : 0;
-			const int dt = op != 1 ? l : 0, dq = op != 2 ? l : 0;
-			it = cov_incl_add(dt);
-			const int iq = cov_incl_add(dq);
-			my_t0 = it - dt, my_q0 = qoff + iq - dq;
-			tot_t = __shfl(it, 63), tot_q = __shfl(iq, 63);
-		};
-		load();
-		unsigned long long p_ref = 0, p_alt = 0;                // the statements of the 64 sites before
-		for (int c0 = s_lo; c0 < s_hi; c0 += 64) {
-			const int s = c0 + lane;
-			const bool valid = s < s_hi;
-			const int p = valid ? L.pos[s] : 0, al = valid ? (int)L.alt[s] : 0;
-			int stmt = 0;                                         // 1: REF, 2: ALT
-			bool done = !valid;
-			for (;;) {                                            // (every lane of the wave runs it: the exits are the wave's)
-				const bool mine = !done && p < toff + tot_t;        // (p >= toff: the chunks before have been left behind by this lane)
-				const int rel = mine ? (int)(p - toff) : 0;
-				int o = 0;                                          // this site's operation: the first whose inclusive advance exceeds rel
-				for (int step = 32; step > 0; step >>= 1) {
-					const int e = __shfl(it, o + step - 1);
-					if (e <= rel) o += step;
-				}
-				const int o_op = __shfl(op, o), t0 = __shfl(my_t0, o), q0 = __shfl(my_q0, o);
-				if (mine) {
-					if (o_op == 0) {
-						const int qc = Q(q0 + rel - t0), tc = pile_ref(B.seq4, coff + p);
-						stmt = al < 4 && qc == al ? 2 : tc < 4 && qc == tc ? 1 : 0;
-					} else if (o_op == 2) stmt = al == CH_DEL ? 2 : 0;
-					done = true;
-				}
-				if (!__ballot(!done)) break;
-				toff += tot_t, qoff += tot_q, k0 += 64;
-				if (k0 >= n_c) { tot_t = tot_q = 0; break; }        // (a site behind the CIGAR's end: none, re is its end)
-				load();
+	}, [&](int, int s, bool valid, int stmt) {
+		const unsigned long long c_ref = __ballot(stmt == 1), c_alt = __ballot(stmt == 2);
+		const int nb = valid ? min(W, s - s_lo) : 0;             // the sites in front of this one, in the window and in the record's range
+		if (stmt) link_put(L.site + (int64_t)s * 2 + (stmt - 1), 1);
+		if (nb > 0) {
+			// sites s - 64 .. s - 1 as bits 0 .. 63: site s - d - 1 is bit 63 - d
+			const unsigned long long v_ref = lane ? (p_ref >> lane) | (c_ref << (64 - lane)) : p_ref;
+			const unsigned long long v_alt = lane ? (p_alt >> lane) | (c_alt << (64 - lane)) : p_alt;
+			unsigned long long todo = ~0ull << (64 - nb);
+			if (stmt == 1) todo &= ~v_ref;                        // REF / REF is derived
+			while (todo) {
+				const int b = 63 - __clzll((long long)todo), d = 63 - b;
+				todo &= ~(1ull << b);
+				const int a_i = (v_alt >> b & 1ull) ? 1 : (v_ref >> b & 1ull) ? 0 : -1;
+				const int cell = a_i < 0 || !stmt ? 0 : 2 * a_i + (stmt - 1);
+				link_put(L.pair + ((int64_t)(s - d - 1) * W + d) * 4 + cell, 1);
 			}
-			const unsigned long long c_ref = __ballot(stmt == 1), c_alt = __ballot(stmt == 2);
-			const int nb = valid ? min(W, s - s_lo) : 0;           // the sites in front of this one, in the window and in the record's range
-			if (stmt) link_put(L.site + (int64_t)s * 2 + (stmt - 1), 1);
-			if (nb > 0) {
-				// sites s - 64 .. s - 1 as bits 0 .. 63: site s - d - 1 is bit 63 - d
-				const unsigned long long v_ref = lane ? (p_ref >> lane) | (c_ref << (64 - lane)) : p_ref;
-				const unsigned long long v_alt = lane ? (p_alt >> lane) | (c_alt << (64 - lane)) : p_alt;
-				unsigned long long todo = ~0ull << (64 - nb);
-				if (stmt == 1) todo &= ~v_ref;                      // REF / REF is derived
-				while (todo) {
-					const int b = 63 - __clzll((long long)todo), d = 63 - b;
-					todo &= ~(1ull << b);
-					const int a_i = (v_alt >> b & 1ull) ? 1 : (v_ref >> b & 1ull) ? 0 : -1;
-					const int cell = a_i < 0 || !stmt ? 0 : 2 * a_i + (stmt - 1);
-					link_put(L.pair + ((int64_t)(s - d - 1) * W + d) * 4 + cell, 1);
-				}
-			}
-			p_ref = c_ref, p_alt = c_alt;
 		}
+		p_ref = c_ref, p_alt = c_alt;
 	});
 }
 
@@ -233,7 +157,7 @@ const Accum *as_accum(const mnc_linkage *lk) { return lk; }
 int linkage_add(mnc_linkage *lk, const Batch &B, int sel, hipStream_t st)
 {
 	if (B.n_reads == 0 || lk->n_sites == 0) return MNC_OK;
-	const LinkView L{lk->d_pos, lk->d_first, lk->d_alt, lk->d_off, lk->n_contigs, lk->window, lk->site, lk->pair, lk->track};
+	const LinkView L{lk->list.view(lk->n_contigs), lk->window, lk->site, lk->pair, lk->track};
 	return lk->add(st, [&] { hipLaunchKernelGGL(mnc_link_add, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, L); });
 }
 
@@ -247,63 +171,23 @@ extern "C" void mnc_linkage_free(mnc_linkage *lk)
 	delete lk;
 }
 
-// a site's allele as the kernel holds it; -1: none of A C G T -
-static int link_allele(uint8_t c)
-{
-	switch (c) {
-	case 'A': return 0;
-	case 'C': return 1;
-	case 'G': return 2;
-	case 'T': return 3;
-	case '-': return CH_DEL;
-	default: return -1;
-	}
-}
-
 extern "C" int mnc_linkage_create(mnc_index *idx, int device, const mnc_variant_t *sites, int64_t n_sites, int32_t window, mnc_linkage **out)
 {
 	if (!idx || !out) return MNC_ERR_ARG;
 	*out = nullptr;
 	if (n_sites < 0 || (n_sites && !sites)) return MNC_ERR_ARG;
 	if (window < 1 || window > MNC_LINKAGE_MAX_WINDOW) { set_error("window %d outside 1 .. %d", (int)window, MNC_LINKAGE_MAX_WINDOW); return MNC_ERR_ARG; }
-	if (n_sites > MNC_LINKAGE_MAX_SITES) { set_error("%lld sites, at most %lld", (long long)n_sites, (long long)MNC_LINKAGE_MAX_SITES); return MNC_ERR_ARG; }
-	if (idx->seq_off.size() != idx->contig_len.size() + 1) { set_error("the index holds no contig bases"); return MNC_ERR_ARG; }
-	const int n_contigs = (int)idx->contig_len.size();
+	LinkSitesHost H;
+	if (int rc = link_sites_check(idx, sites, n_sites, H)) return rc;
+	const int n_contigs = H.n_contigs;
 	mnc_linkage *lk = new (std::nothrow) mnc_linkage;
 	if (!lk) return MNC_ERR_NOMEM;
-	std::vector<int32_t> pos, rid, first;
-	std::vector<uint8_t> alt;
-	std::vector<int64_t> off;
-	try {
-		pos.resize((size_t)n_sites), rid.resize((size_t)n_sites), alt.resize((size_t)n_sites), first.assign((size_t)n_contigs + 1, 0);
-		off.assign(idx->seq_off.begin(), idx->seq_off.end());
-	} catch (const std::bad_alloc &) { delete lk; return MNC_ERR_NOMEM; }
-	for (int64_t i = 0; i < n_sites; ++i) {
-		const mnc_variant_t &v = sites[i];
-		const int a = link_allele(v.alt);
-		if (v.alt == '+') set_error("site %lld is an insertion allele ('+'): linkage takes A C G T and '-'", (long long)i);
-		else if (a < 0) set_error("site %lld: allele 0x%02x is none of A C G T -", (long long)i, (unsigned)v.alt);
-		else if (v.rid < 0 || v.rid >= n_contigs || v.pos < 0 || v.pos >= off[v.rid + 1] - off[v.rid])
-			set_error("site %lld: position %d of contig %d is outside the index", (long long)i, (int)v.pos, (int)v.rid);
-		else if (i && (v.rid < rid[i - 1] || (v.rid == rid[i - 1] && (v.pos < pos[i - 1] || (v.pos == pos[i - 1] && a <= (int)alt[i - 1])))))
-			set_error("site %lld does not ascend strictly in (rid, pos, allele A C G T -)", (long long)i);
-		else {
-			pos[i] = v.pos, rid[i] = v.rid, alt[i] = (uint8_t)a, first[v.rid + 1] += 1;
-			continue;
-		}
-		delete lk;
-		return MNC_ERR_ARG;
-	}
-	for (int c = 0; c < n_contigs; ++c) first[c + 1] += first[c];
 	if (int rc = check_device(device)) { delete lk; return rc; }
 	lk->n_sites = n_sites, lk->window = window, lk->n_contigs = n_contigs;
-	const size_t ns = (size_t)n_sites, nc = (size_t)n_contigs, nw = (size_t)lk->words();
+	const size_t ns = (size_t)n_sites, nw = (size_t)lk->words();
 	hipError_t he = lk->begin(idx, device);
-	lk->alloc(he, (void**)&lk->d_pos, ns * 4);
+	lk->list.alloc(*lk, he, H);
 	lk->alloc(he, (void**)&lk->d_rid, ns * 4);
-	lk->alloc(he, (void**)&lk->d_alt, ns);
-	lk->alloc(he, (void**)&lk->d_first, (nc + 1) * 4);
-	lk->alloc(he, (void**)&lk->d_off, (nc + 1) * 8);
 	lk->alloc(he, (void**)&lk->site, ns * 8);
 	lk->alloc(he, (void**)&lk->pair, nw * 4);
 	lk->alloc(he, (void**)&lk->run0, (ns + 1) * 8);
@@ -314,11 +198,8 @@ extern "C" int mnc_linkage_create(mnc_index *idx, int device, const mnc_variant_
 	lk->alloc(he, (void**)&lk->o_phase, ns);
 	lk->streams(he);
 	if (he == hipSuccess) lk->track = lk->pair + ns * (size_t)window * 4;
-	if (he == hipSuccess && ns) he = hipMemcpy(lk->d_pos, pos.data(), ns * 4, hipMemcpyHostToDevice);
-	if (he == hipSuccess && ns) he = hipMemcpy(lk->d_rid, rid.data(), ns * 4, hipMemcpyHostToDevice);
-	if (he == hipSuccess && ns) he = hipMemcpy(lk->d_alt, alt.data(), ns, hipMemcpyHostToDevice);
-	if (he == hipSuccess) he = hipMemcpy(lk->d_first, first.data(), (nc + 1) * 4, hipMemcpyHostToDevice);
-	if (he == hipSuccess) he = hipMemcpy(lk->d_off, off.data(), (nc + 1) * 8, hipMemcpyHostToDevice);
+	lk->list.fill(he, H);
+	if (he == hipSuccess && ns) he = hipMemcpy(lk->d_rid, H.rid.data(), ns * 4, hipMemcpyHostToDevice);
 	if (he != hipSuccess) {
 		set_error("linkage accumulator of %lld sites, window %d (%d bytes a site): %s", (long long)n_sites, (int)window, 20 * window + 50, hipGetErrorString(he));
 		const int rc = Accum::failed(he);

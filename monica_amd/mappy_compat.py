@@ -343,6 +343,11 @@ class Aligner:
         index on this object's device: pass it to `map_batch` in a second pass over the reads, then `phase()` it."""
         return _capi.Linkage(self._index, sites, window, self._device)
 
+    def haplotag(self, sites, block, phase, cap_reads, min_votes=2, min_permille=600):
+        """A haplotag accumulator (`_capi.Haplotag`) over `sites` with the `block` / `phase` that `linkage().phase()` gave, for
+        batches of at most `cap_reads` reads: pass it to `map_batch` in a third pass, then read `blocks()` and `tags()`."""
+        return _capi.Haplotag(self._index, sites, block, phase, cap_reads, min_votes, min_permille, self._device)
+
     def abundance(self, cap_cands=_capi.ABUNDANCE_CAP_CANDS, max_delta=_capi.ABUNDANCE_MAX_DELTA, scale_q=_capi.ABUNDANCE_SCALE_Q):
         """An abundance accumulator (`_capi.Abundance`) for this index on this object's device: pass it to `map_batch`,
         then `solve()` it."""
@@ -358,7 +363,8 @@ class Aligner:
         return _capi.Abundance.global_(self._device, len(genome_names), cap_cands, max_delta, scale_q, genome_names=genome_names)
 
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
-                  abundance=None, quals=None, linkage=None, linkage_what=_capi.COV_GATED):
+                  abundance=None, quals=None, linkage=None, linkage_what=_capi.COV_GATED,
+                  haplotag=None, haplotag_what=_capi.COV_GATED):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
@@ -366,7 +372,8 @@ class Aligner:
         `pileup` (an accumulator of `pileup()`) likewise, `pileup_what` one selector; with `abundance` (an accumulator of
         `abundance()`) every read's candidate genomes are added to it.  `quals`: the batch's Phred+33 characters at
         `offsets`, for a `pileup(strands=min_qual)` that masks by base quality.  With `linkage` (an accumulator of
-        `linkage()`) the batch is added to it, `linkage_what` one selector."""
+        `linkage()`) the batch is added to it, `linkage_what` one selector; with `haplotag` (an accumulator of `haplotag()`)
+        likewise, `haplotag_what` one selector, and its `tags()` are this batch's."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -383,6 +390,8 @@ class Aligner:
             eng.add_abundance(abundance)
         if linkage is not None:
             eng.add_linkage(linkage, linkage_what)
+        if haplotag is not None:
+            eng.add_haplotag(haplotag, haplotag_what)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
