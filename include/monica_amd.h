@@ -848,6 +848,41 @@ int  mnc_haplotag_fetch_tags(mnc_haplotag *ht, int64_t n_reads, int32_t *tag /* 
  * be NULL.  Ordered behind the adds only after a read-out call or a sync of the engines that added. */
 int  mnc_haplotag_device(mnc_haplotag *ht, const int32_t **d_blk, const int32_t **d_tag);
 
+/* ---------------------------------------------------------------- phased pileup
+ * The sequence of each strain: the per-base counts, the variants and the consensus of haplotype 0 and of haplotype 1,
+ * separately.  mnc_pileup mixes all reads and mnc_haplotag_fetch_tags gives one tag per read, but a record that crosses two
+ * phase blocks may sit on side 0 of one and on side 1 of the other.  mnc_engine_add_pileup_phased makes the haplotag's
+ * decision per (selected record, block) and sends every column of the record to the planes of the haplotype it was decided
+ * for in the block the column lies in (csrc/k_pile_phase.hip: one kernel on the engine's stream, no host wait).  The
+ * destinations are ordinary mnc_pileup accumulators of the engine's index and device: mnc_pileup_fetch_counts,
+ * _call_variants, _consensus and _device serve each haplotype as they stand.  Integer arithmetic throughout.
+ *
+ * `ht` supplies the site list, block[], phase[], min_votes and min_permille and is only read: its block table, its tags and
+ * the read count of its last add are not touched, and cap_reads plays no part.
+ * Extent of block b: the reference interval [pos[first site of b], pos[last site of b]] of its contig, both ends included,
+ * over the whole list (not over the sites under a record).
+ * Block of a reference position p of contig c: let i be the first site of c with pos[i] >= p.  If pos[i] == p, block[i];
+ * else, if site i - 1 lies on c and block[i - 1] == block[i], that block; else p lies in no block.  (Where two sites share a
+ * position and lie in different blocks, the lower block owns the position.)
+ * Decision per (selected record, block): the haplotag section's, word for word.
+ * Destination of a column of a selected record:
+ *   an M or D column at p   hap0 or hap1 if p lies in a block in which THIS record is DECIDED, for that side; else `rest` (no
+ *                           block, an undecided block, a block in which the record said nothing, no site under the record)
+ *   an I operation          where its anchor column p - 1 goes; counted where and when the plain pileup counts it
+ *   rest == NULL            those observations are dropped; hap0 and hap1 are bit for bit what they are with a rest
+ * A destination receives what mnc_engine_add_pileup would have given it for those columns alone (depth for M columns, a base
+ * / N / DEL / INS count by the pileup's rules, the contig-end rule).  So, with a rest, the eight fetch_counts planes of the
+ * three accumulators sum, base by base, to those of one plain pileup of the same batch and selector.  Every word is
+ * additive: the result does not depend on order or on how a sample was cut into batches.
+ *
+ * Returns, before anything is touched: whatever mnc_engine_add_haplotag refuses for eng / ht / what, with its codes
+ * (MNC_ERR_UNSUPPORTED after a call that ran both passes included; not MNC_ERR_RANGE: cap_reads plays no part); MNC_ERR_ARG
+ * when a pileup is of another index or device than the engine's, when two of the three pileups are the same object, or when
+ * one of them has the insertion store or the strand store on (the allele table and the strand planes by haplotype are a
+ * later addition; the message says so).  A successful call counts as an add for each pileup: a later mnc_pileup_store_* on
+ * it is refused as after any add. */
+int  mnc_engine_add_pileup_phased(mnc_engine *eng, const mnc_haplotag *ht, mnc_pileup *hap0, mnc_pileup *hap1, mnc_pileup *rest /* may be NULL */, int what);
+
 /* ---------------------------------------------------------------- abundance
  * Which of several close genomes is in the sample, and how much of each: the other half of the focus pass' question.  The
  * count table cannot answer it -- a read counts only with a primary hit of mapq >= min_mapq, and against genomes 0.5-1 %

@@ -102,6 +102,7 @@ EXPORTS = [
     "mnc_linkage_fetch_sites", "mnc_linkage_fetch_pairs", "mnc_linkage_phase", "mnc_linkage_device",
     "mnc_haplotag_create", "mnc_haplotag_free", "mnc_haplotag_reset", "mnc_haplotag_device_bytes", "mnc_haplotag_n_blocks",
     "mnc_engine_add_haplotag", "mnc_haplotag_fetch_blocks", "mnc_haplotag_fetch_tags", "mnc_haplotag_device",
+    "mnc_engine_add_pileup_phased",
     "mnc_abundance_create", "mnc_abundance_free", "mnc_abundance_reset", "mnc_abundance_device_bytes", "mnc_engine_add_abundance",
     "mnc_abundance_add_lists", "mnc_abundance_info", "mnc_abundance_fetch_unique", "mnc_abundance_fetch_lists", "mnc_abundance_solve",
     "mnc_abundance_device", "mnc_abundance_create_global", "mnc_abundance_add_carry",
@@ -284,6 +285,7 @@ def lib():
     sig("mnc_haplotag_fetch_blocks", i32, [vp, i64, i64, vp])
     sig("mnc_haplotag_fetch_tags", i32, [vp, i64, vp, vp])
     sig("mnc_haplotag_device", i32, [vp, pp, pp])
+    sig("mnc_engine_add_pileup_phased", i32, [vp, vp, vp, vp, vp, i32])
     sig("mnc_abundance_create", i32, [vp, i32, i64, C.c_int32, C.c_int32, pp])
     sig("mnc_abundance_free", None, [vp])
     sig("mnc_abundance_reset", i32, [vp])
@@ -665,6 +667,14 @@ class Engine:
         write its reads' tags.  `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
         self._add("mnc_engine_add_haplotag", haplotag, int(what))
         haplotag.n_reads = self.n_reads
+
+    def add_pileup_phased(self, haplotag, hap0, hap1, rest=None, what=COV_GATED):
+        """`mnc_engine_add_pileup_phased`: add the last classified batch, as it stands in HBM, to the pileups `hap0` and
+        `hap1` -- every column of a selected record to the haplotype the record is decided for in the phase block the column
+        lies in, by the site list, blocks, phases and thresholds of `haplotag` (which is only read) -- and whatever has no
+        such haplotype to `rest` (None: dropped).  `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.
+        Asynchronous."""
+        check(lib().mnc_engine_add_pileup_phased(self._h, haplotag._h, hap0._h, hap1._h, rest._h if rest is not None else None, int(what)))
 
     def add_abundance(self, abundance):
         """`mnc_engine_add_abundance`: add the candidate genomes of every read of the last classified batch, as it stands in

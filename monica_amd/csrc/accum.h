@@ -9,6 +9,8 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <functional>
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
@@ -108,6 +110,33 @@ struct Accum {
 		return MNC_ERR_HIP;
 	}
 };
+
+// Accum::add for a SET of accumulators that one launch writes (the phased pileup's two or three planes sets): `set` holds n <= 4
+// accumulators of one device, no two the same, nullptr entries left out.  Their mutexes are taken in address order, so two
+// threads that add to overlapping sets cannot wait for each other; the launch comes behind every one's last reset, and every
+// one's reset and read-outs come behind it.
+template <class F>
+int accum_add_set(Accum *const *set, int n, hipStream_t on, F launch)
+{
+	Accum *a[4];
+	int m = 0;
+	for (int i = 0; i < n && m < 4; ++i)
+		if (set[i]) a[m++] = set[i];
+	std::sort(a, a + m, std::less<Accum*>());
+	std::unique_lock<std::mutex> lk[4];
+	for (int i = 0; i < m; ++i) lk[i] = std::unique_lock<std::mutex>(a[i]->mu);
+	for (int i = 0; i < m; ++i) {
+		HIP_TRY(hipStreamWaitEvent(on, a[i]->ev_own, 0));
+		if (a[i]->serial) HIP_TRY(hipStreamWaitEvent(on, a[i]->ev_add, 0));
+	}
+	launch();
+	HIP_TRY(hipGetLastError());
+	for (int i = 0; i < m; ++i) {
+		HIP_TRY(hipEventRecord(a[i]->ev_add, on));
+		HIP_TRY(hipStreamWaitEvent(a[i]->st, a[i]->ev_add, 0));
+	}
+	return MNC_OK;
+}
 
 inline int accum_device_bytes(const Accum *a, int64_t *bytes)
 {

@@ -111,6 +111,8 @@ int linkage_add(mnc_linkage *lk, const Batch &B, int sel, hipStream_t st);
 const Accum *as_accum(const mnc_haplotag *ht);              // k_haplotag.hip
 int haplotag_fits(const mnc_haplotag *ht, const Batch &B);
 int haplotag_add(mnc_haplotag *ht, const Batch &B, int sel, hipStream_t st);
+int pile_phase_check(const mnc_pileup *hap0, const mnc_pileup *hap1, const mnc_pileup *rest);   // k_pile_phase.hip
+int pile_phase_add(const mnc_haplotag *ht, mnc_pileup *hap0, mnc_pileup *hap1, mnc_pileup *rest, const Batch &B, int sel, hipStream_t st);
 // the candidate carry (k_carry.hip): an Accum of a device, of no index
 const Accum *as_accum(const mnc_carry *cc);
 int carry_add(mnc_carry *cc, const Batch &B, int n_contigs, int n_genomes, int64_t first_read, int32_t genome_offset, hipStream_t st);
@@ -1818,6 +1820,24 @@ extern "C" int mnc_engine_add_haplotag(mnc_engine *e, mnc_haplotag *ht, int what
 	if (int rc = haplotag_fits(ht, e->B)) return rc;
 	HIP_TRY(hipSetDevice(e->device));
 	return haplotag_add(ht, e->B, sel, e->stream);
+}
+
+// ---------------------------------------------------------------- phased pileup of the last batch
+// The haplotag's vote fused with the pileup's column walk (k_pile_phase.hip): haplotag's checks on `ht` -- which is only read,
+// so its tag buffer's capacity plays no part -- and the pileup's on each accumulator; one kernel on the engine's stream.
+extern "C" int mnc_engine_add_pileup_phased(mnc_engine *e, const mnc_haplotag *ht, mnc_pileup *hap0, mnc_pileup *hap1, mnc_pileup *rest, int what)
+{
+	if (!e || !ht || !hap0 || !hap1) return MNC_ERR_ARG;
+	int sel = 0;
+	if (int rc = add_selector(what, true, &sel)) return rc;
+	if (int rc = add_precheck(e, as_accum(ht), "phased pileup", "a phased pileup needs the CIGARs of MNC_CONTRACT_DP")) return rc;
+	for (const mnc_pileup *pu : {hap0, hap1, rest})
+		if (pu)
+			if (int rc = add_precheck(e, as_accum(pu), "phased pileup", nullptr)) return rc;
+	if (int rc = pile_phase_check(hap0, hap1, rest)) return rc;
+	if (e->B.n_reads == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return pile_phase_add(ht, hap0, hap1, rest, e->B, sel, e->stream);
 }
 
 // ... with the batch's quality characters, for a pileup with the strand store (k_pile_strand.hip).  A host array goes to a

@@ -40,17 +40,6 @@ struct mnc_haplotag : mnc::Accum {
 
 namespace mnc {
 
-struct HapView {
-	LinkSites list;
-	const int32_t *block;
-	const uint8_t *phase;
-	int min_votes, min_permille;
-	int32_t *blk, *tag, *votes;
-};
-
-// bits [lo, hi) of a 64-bit mask, 0 <= lo < hi <= 64
-__device__ __forceinline__ unsigned long long hap_bits(int lo, int hi) { return (hi < 64 ? (1ull << hi) - 1ull : ~0ull) & ~((1ull << lo) - 1ull); }
-
 __global__ __launch_bounds__(256) void mnc_hap_add(Batch B, int sel, HapView H)
 {
 	const int lane = lane_id();
@@ -60,21 +49,9 @@ __global__ __launch_bounds__(256) void mnc_hap_add(Batch B, int sel, HapView H)
 	int s_hi = 0;
 	int cb = -1, cn0 = 0, cn1 = 0;                            // the open block carried over the last 64 sites' border
 	link_walk(B, rd, sel, H.list, [&](int, int hi) { s_hi = hi, cb = -1, cn0 = cn1 = 0; }, [&](int c0, int s, bool valid, int stmt) {
-		const int b = valid ? H.block[s] : -1;
-		const int hap = stmt ? (stmt - 1) ^ (int)H.phase[s] : -1;
-		const unsigned long long v0 = __ballot(hap == 0), v1 = __ballot(hap == 1);
-		const int below = __shfl_up(b, 1);
-		const bool head = valid && b != (lane ? below : cb);
-		const unsigned long long heads = __ballot(head), starts = heads | 1ull;   // (lane 0 is valid: c0 < s_hi)
-		// ---- this lane's segment, if it owns one: [lane, the next head)
-		const unsigned long long above = lane < 63 ? heads & (~0ull << (lane + 1)) : 0ull;
-		const bool owner = valid && (head || lane == 0);
-		const bool more = c0 + 64 < s_hi && H.block[c0 + 64] == H.block[c0 + 63];   // wave-uniform: the last segment stays open
-		const unsigned long long seg = hap_bits(lane, above ? __ffsll((long long)above) - 1 : 64);
-		const int n0 = __popcll(v0 & seg) + (lane == 0 && !head ? cn0 : 0), n1 = __popcll(v1 & seg) + (lane == 0 && !head ? cn1 : 0);
-		const int tot = n0 + n1, diff = n0 > n1 ? n0 - n1 : n1 - n0;
-		const bool closes = owner && (above || !more) && tot > 0;  // (a block in which the record said nothing is not touched)
-		const bool decided = closes && tot >= H.min_votes && diff && (long long)diff * 1000 >= (long long)H.min_permille * tot;
+		const HapSeg g = hap_segment(H.block, H.phase, c0, s, valid, stmt, s_hi, cb, cn0, cn1);
+		const int b = g.b, n0 = g.n0, n1 = g.n1, diff = n0 > n1 ? n0 - n1 : n1 - n0;
+		const bool closes = g.closes, decided = closes && hap_decided(n0, n1, H.min_votes, H.min_permille);
 		if (closes) {
 			int32_t *w = H.blk + (int64_t)b * 4;
 			link_put(w + (decided ? (int)(n1 > n0) : 2), 1);
@@ -87,14 +64,6 @@ __global__ __launch_bounds__(256) void mnc_hap_add(Batch B, int sel, HapView H)
 			best = x0 > x1 ? x0 - x1 : x1 - x0, best_n0 = x0, best_n1 = x1, best_tag = __shfl(b, l) * 2 + (int)(x1 > x0);
 			cand = l < 63 ? __ballot(decided && diff > best) & (~0ull << (l + 1)) : 0ull;
 		}
-		// ---- what crosses the border: the last segment's counts, from the masks (the same in every lane)
-		if (more) {
-			const int ls = 63 - __clzll((long long)starts);
-			const unsigned long long last = hap_bits(ls, 64);
-			const bool joins = ls == 0 && !(heads & 1ull);          // the whole 64 sites continue the block carried in
-			cn0 = __popcll(v0 & last) + (joins ? cn0 : 0), cn1 = __popcll(v1 & last) + (joins ? cn1 : 0);
-			cb = H.block[c0 + 63];
-		} else cb = -1, cn0 = cn1 = 0;
 	});
 	if (lane == 0) {
 		H.tag[rd] = best_tag;
@@ -113,9 +82,14 @@ int haplotag_fits(const mnc_haplotag *ht, const Batch &B)
 	return MNC_ERR_RANGE;
 }
 
+HapView haplotag_view(const mnc_haplotag *ht)
+{
+	return HapView{ht->list.view(ht->n_contigs), ht->d_block, ht->d_phase, ht->min_votes, ht->min_permille, ht->blk, ht->tag, ht->votes};
+}
+
 int haplotag_add(mnc_haplotag *ht, const Batch &B, int sel, hipStream_t st)
 {
-	const HapView H{ht->list.view(ht->n_contigs), ht->d_block, ht->d_phase, ht->min_votes, ht->min_permille, ht->blk, ht->tag, ht->votes};
+	const HapView H = haplotag_view(ht);
 	return ht->add(st, [&] {
 		ht->last_reads = B.n_reads;
 		if (B.n_reads) hipLaunchKernelGGL(mnc_hap_add, dim3((B.n_reads + 3) / 4), dim3(256), 0, st, B, sel, H);

@@ -364,7 +364,7 @@ class Aligner:
 
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
                   abundance=None, quals=None, linkage=None, linkage_what=_capi.COV_GATED,
-                  haplotag=None, haplotag_what=_capi.COV_GATED):
+                  haplotag=None, haplotag_what=_capi.COV_GATED, phased=None, phased_what=_capi.COV_GATED):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
@@ -373,7 +373,9 @@ class Aligner:
         `abundance()`) every read's candidate genomes are added to it.  `quals`: the batch's Phred+33 characters at
         `offsets`, for a `pileup(strands=min_qual)` that masks by base quality.  With `linkage` (an accumulator of
         `linkage()`) the batch is added to it, `linkage_what` one selector; with `haplotag` (an accumulator of `haplotag()`)
-        likewise, `haplotag_what` one selector, and its `tags()` are this batch's."""
+        likewise, `haplotag_what` one selector, and its `tags()` are this batch's; with `phased` = (haplotag, hap0, hap1,
+        rest or None) -- an accumulator of `haplotag()` and pileups of `pileup()` -- the batch's columns are added to the
+        pileup of the haplotype their record is decided for (`Engine.add_pileup_phased`), `phased_what` one selector."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -392,6 +394,8 @@ class Aligner:
             eng.add_linkage(linkage, linkage_what)
         if haplotag is not None:
             eng.add_haplotag(haplotag, haplotag_what)
+        if phased is not None:
+            eng.add_pileup_phased(*phased, what=phased_what)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
