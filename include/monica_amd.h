@@ -207,6 +207,9 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   a linkage window outside 1 .. 64, more than  mnc_linkage_create: MNC_ERR_ARG (a lane looks back over the 64 sites in front
  *   2^30 sites, a '+' site, an unsorted list     of its own; insertion alleles are not linked)
  *   2^31 or more records at one site or pair     outside the contract: every word of mnc_linkage holds int32
+ *   a reach outside 1 .. the window              mnc_linkage_phase_window: MNC_ERR_ARG
+ *   a table with a negative count, or a count    mnc_linkage_add_tables: MNC_ERR_ARG, the accumulator untouched, the message
+ *   in a cell past its contig's last site        names the cell
  *   haplotags after a call that ran both the     mnc_engine_add_haplotag: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
  *   usual and the wide pass; under               linkage); MNC_ERR_ARG under MNC_CONTRACT_CHAIN (no CIGAR to take the columns
  *   MNC_CONTRACT_CHAIN                           from)
@@ -785,6 +788,38 @@ int  mnc_linkage_fetch_pairs(mnc_linkage *lk, int64_t first, int64_t n, int32_t 
  * every contig's first site, starts a block.  block[i] = the block starts before or at i, minus one; phase[i] = 0 at a block
  * start, else phase[i - 1] XOR (trans > cis). */
 int  mnc_linkage_phase(mnc_linkage *lk, int32_t min_pairs, int32_t min_permille, int32_t *block /* [n_sites] */, uint8_t *phase /* [n_sites] */);
+/* Phase blocks from the WHOLE window: every pair (j, i), j < i on one contig, d = i - j - 1 < reach (1 .. the window) takes
+ * part, so a site that is linked to nothing -- a homopolymer deletion, chance errors that crossed the caller's thresholds --
+ * no longer cuts a block: the true site behind it is linked to the true site in front of it.  One answer whatever the launch
+ * shape; integers only.
+ *   link      (n00, n01, n10, n11) = pair[j][d] as mnc_linkage_fetch_pairs yields it.  cis, trans, tot as for
+ *             mnc_linkage_phase, diff = |cis - trans|; j and i are linked iff tot >= min_pairs, cis != trans and
+ *             diff * 1000 >= min_permille * tot (int64); the link's orientation is trans > cis.
+ *   parent    p(i): among the earlier sites linked to i the one with the largest diff, ties to the nearest (smallest d).  A
+ *             site without one is a root.
+ *   start     site k starts an interval iff no site i >= k has p(i) < k (no parent edge passes over or ends at the boundary
+ *             in front of k; only i < k + reach can).  Every contig's first site is a start; every start is a root.
+ *   kept      r(i): the root the parents lead to from i.  Site i is kept iff r(i) is a start (it is then the start of the
+ *             interval i lies in).  Dropped: an isolated site under a parent edge, and any tree that floats inside another
+ *             tree's interval.
+ * block[i] = the starts before or at i, minus one, for a kept site, -1 for a dropped one; phase[i] = the XOR of the
+ * orientations on the path from i to r(i), 0 at a start and for a dropped site; *n_kept (may be NULL) = the kept sites.
+ * Two consequences.  With reach = 1 nothing is dropped and block[] / phase[] are bit for bit mnc_linkage_phase's.  Over the
+ * kept sites alone block[] starts at 0 and ascends by steps of 0 or 1, and every contig's first kept site starts a block:
+ * the list, block[] and phase[] compacted to the kept sites are what mnc_haplotag_create demands, as they stand.
+ * MNC_ERR_ARG: a NULL lk, reach outside 1 .. the window, a NULL block or phase with n_sites > 0.  Waits and threading as
+ * mnc_linkage_phase; the scan of the track's first `reach` columns (8 * reach + 8 bytes per site) is allocated for the call
+ * and freed by it, so mnc_linkage_device_bytes and mnc_linkage_create's MNC_ERR_NOMEM rule do not know it. */
+int  mnc_linkage_phase_window(mnc_linkage *lk, int32_t reach, int32_t min_pairs, int32_t min_permille,
+                              int32_t *block /* [n_sites] */, uint8_t *phase /* [n_sites] */, int64_t *n_kept);
+/* Adds tables as mnc_linkage_fetch_sites / _fetch_pairs write them (n00 included) -- another rank's, another engine's
+ * accumulator over the same list, a file's: the counterpart of mnc_pileup_add_insertion_list.  On the device n01, n10, n11
+ * go onto their words and track[i][d] += T[i][d] - T[i - 1][d], T the sum of a cell's four counts, T[-1] = 0; afterwards
+ * mnc_linkage_fetch_pairs returns what it returned before plus the tables, cell by cell.  MNC_ERR_ARG, the accumulator
+ * untouched and the message naming the cell: a negative count; a non-zero cell whose j lies past its contig's last site (zero
+ * in every table an accumulator produces; such cells keep every track column summing to zero).  An engine's later add comes
+ * behind it; the call returns when the host arrays have been read. */
+int  mnc_linkage_add_tables(mnc_linkage *lk, const int32_t *site /* [n_sites][2] */, const int32_t *pair /* [n_sites][window][4] */);
 /* The raw additive words (device pointers, laid out as above; either may be NULL), for a collective of the caller's.  Ordered
  * behind the adds only after a read-out call or a sync of the engines that added. */
 int  mnc_linkage_device(mnc_linkage *lk, const int32_t **d_site, const int32_t **d_pair);

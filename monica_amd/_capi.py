@@ -100,6 +100,7 @@ EXPORTS = [
     "mnc_pileup_store_strands", "mnc_engine_add_pileup_quals", "mnc_pileup_fetch_strand_counts", "mnc_pileup_call_variants_strands", "mnc_pileup_strands_device",
     "mnc_linkage_create", "mnc_linkage_free", "mnc_linkage_reset", "mnc_linkage_device_bytes", "mnc_engine_add_linkage",
     "mnc_linkage_fetch_sites", "mnc_linkage_fetch_pairs", "mnc_linkage_phase", "mnc_linkage_device",
+    "mnc_linkage_phase_window", "mnc_linkage_add_tables",
     "mnc_haplotag_create", "mnc_haplotag_free", "mnc_haplotag_reset", "mnc_haplotag_device_bytes", "mnc_haplotag_n_blocks",
     "mnc_engine_add_haplotag", "mnc_haplotag_fetch_blocks", "mnc_haplotag_fetch_tags", "mnc_haplotag_device",
     "mnc_engine_add_pileup_phased",
@@ -276,6 +277,8 @@ def lib():
     sig("mnc_linkage_fetch_pairs", i32, [vp, i64, i64, vp])
     sig("mnc_linkage_phase", i32, [vp, i32, i32, vp, vp])
     sig("mnc_linkage_device", i32, [vp, pp, pp])
+    sig("mnc_linkage_phase_window", i32, [vp, i32, i32, i32, vp, vp, C.POINTER(i64)])
+    sig("mnc_linkage_add_tables", i32, [vp, vp, vp])
     sig("mnc_haplotag_create", i32, [vp, i32, vp, i64, vp, vp, i64, i32, i32, pp])
     sig("mnc_haplotag_free", None, [vp])
     sig("mnc_haplotag_reset", i32, [vp])
@@ -977,7 +980,8 @@ class Linkage(_Accumulator):
     """Owner of an ``mnc_linkage``: per site of a fixed list (`sites`: a VARIANT_DTYPE array in (rid, pos, allele) order,
     as `Pileup.variants` returns it, without '+' rows) how many records say REF and ALT, and per pair of sites up to
     `window` apart in the list the four joint counts -- accumulated from batch to batch by `Engine.add_linkage`
-    (include/monica_amd.h, "linkage").  `phase()` turns the adjacent pairs into phase blocks on the device."""
+    (include/monica_amd.h, "linkage").  `phase()` turns the adjacent pairs into phase blocks on the device,
+    `phase_window()` every pair of the window, so that a site linked to nothing no longer cuts a block."""
 
     _c = "linkage"
 
@@ -1007,6 +1011,23 @@ class Linkage(_Accumulator):
         check(lib().mnc_linkage_phase(self._h, int(min_pairs), int(min_permille), block.ctypes.data if len(block) else None,
                                       phase.ctypes.data if len(phase) else None))
         return block, phase
+
+    def phase_window(self, reach=None, min_pairs=1, min_permille=0):
+        """`mnc_linkage_phase_window`: (keep bool[n_sites], block int32[n_sites], phase uint8[n_sites]) from every pair less
+        than `reach` sites apart (None: the window).  A dropped site has keep False and block -1; `sites[keep]`,
+        `block[keep]`, `phase[keep]` are what `Haplotag` takes."""
+        block, phase = np.zeros(len(self.sites), dtype=np.int32), np.zeros(len(self.sites), dtype=np.uint8)
+        check(lib().mnc_linkage_phase_window(self._h, self.window if reach is None else int(reach), int(min_pairs), int(min_permille),
+                                             block.ctypes.data if len(block) else None, phase.ctypes.data if len(phase) else None, None))
+        return block >= 0, block, phase
+
+    def add_tables(self, site, pair):
+        """`mnc_linkage_add_tables`: add `site` int32[n_sites, 2] and `pair` int32[n_sites, window, 4] as `site_counts()` and
+        `pairs()` of an accumulator over the same list return them."""
+        site, pair = np.ascontiguousarray(site, dtype=np.int32), np.ascontiguousarray(pair, dtype=np.int32)
+        if site.shape != (len(self.sites), 2) or pair.shape != (len(self.sites), self.window, 4):
+            raise ValueError("site is [n_sites, 2] and pair [n_sites, window, 4]")
+        check(lib().mnc_linkage_add_tables(self._h, site.ctypes.data if site.size else None, pair.ctypes.data if pair.size else None))
 
     def device(self):
         """(device address of site[n_sites][2], of the 5 * n_sites * window raw pair words): `mnc_linkage_device`."""

@@ -343,9 +343,14 @@ class Aligner:
         index on this object's device: pass it to `map_batch` in a second pass over the reads, then `phase()` it."""
         return _capi.Linkage(self._index, sites, window, self._device)
 
-    def haplotag(self, sites, block, phase, cap_reads, min_votes=2, min_permille=600):
+    def haplotag(self, sites, block, phase, cap_reads, min_votes=2, min_permille=600, keep=None):
         """A haplotag accumulator (`_capi.Haplotag`) over `sites` with the `block` / `phase` that `linkage().phase()` gave, for
-        batches of at most `cap_reads` reads: pass it to `map_batch` in a third pass, then read `blocks()` and `tags()`."""
+        batches of at most `cap_reads` reads: pass it to `map_batch` in a third pass, then read `blocks()` and `tags()`.
+        `keep`: the mask that `linkage().phase_window()` returned with its `block` / `phase` -- the three arrays are compacted
+        by it, the dropped sites cast no vote (the accumulator's `sites` are the kept ones)."""
+        if keep is not None:
+            keep = np.asarray(keep, dtype=bool)
+            sites, block, phase = np.asarray(sites)[keep], np.asarray(block)[keep], np.asarray(phase)[keep]
         return _capi.Haplotag(self._index, sites, block, phase, cap_reads, min_votes, min_permille, self._device)
 
     def abundance(self, cap_cands=_capi.ABUNDANCE_CAP_CANDS, max_delta=_capi.ABUNDANCE_MAX_DELTA, scale_q=_capi.ABUNDANCE_SCALE_Q):

@@ -10,7 +10,8 @@ variants ALTERNATING within every repetition of one run on one device, HIP event
   grid w<W>       the same over a site every --grid bases of every contig (an allele that is not the reference's): the load
                   of a sample with that many true variant positions, which the synthetic reads' chance calls do not give
 
-and per site list the wall clock of one phase() over it, the HBM held, and the atomics of one add counted from the words
+and per site list the wall clock of one phase() over it and of one phase_window() at reach 1, 8 and 64 (where the window
+holds it; with its allocation, its copies and its wait, alternating with phase()), the HBM held, and the atomics of one add counted from the words
 as they stand (mnc_linkage_device) beside what one atomic per pair with both statements would have issued.  One JSON
 object on stdout; --out writes it to a file as well."""
 import argparse
@@ -85,7 +86,7 @@ def main():
     res["add_ms"] = {key: {"device_ms": round(float(np.median(v)), 4), "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4),
                            "over_pileup": round(float(np.median(v)) / base, 3)} for key, v in ms.items()}
     # ---- the atomics of one add, from the words as they stand after the last repetition's one add
-    res["atomics_per_batch"], res["phase_wall_ms"] = {}, {}
+    res["atomics_per_batch"], res["phase_wall_ms"], res["phase_window_wall_ms"] = {}, {}, {}
     for key, lk in links.items():
         n, w = len(lk.sites), lk.window
         if not n:
@@ -106,6 +107,17 @@ def main():
             lk.phase(3, 500)
             t.append((time.perf_counter() - t0) * 1e3)
         res["phase_wall_ms"][key] = round(float(np.median(t[args.warmup:])), 4)
+        # ---- phase_window at every reach the window holds, alternating with phase() within every repetition
+        reaches = [r for r in (1, 8, 64) if r <= w]
+        tw = {r: [] for r in [0] + reaches}                       # 0: phase() itself
+        for _ in range(args.warmup + args.reps):
+            for r in tw:
+                t0 = time.perf_counter()
+                lk.phase_window(r, 3, 500) if r else lk.phase(3, 500)
+                tw[r].append((time.perf_counter() - t0) * 1e3)
+        res["phase_window_wall_ms"][key] = {("phase" if r == 0 else f"reach {r}"): {
+            "wall_ms": round(float(np.median(v[args.warmup:])), 4), "min_ms": round(float(np.min(v[args.warmup:])), 4), "max_ms": round(float(np.max(v[args.warmup:])), 4),
+            "cell_bytes_per_site": 16 * r, "kept": int(lk.phase_window(r, 3, 500)[0].sum()) if r else n} for r, v in tw.items()}
     res["note"] = ("pair_words_issued_at_least: the sum of the missing / n01 / n10 / n11 words plus the absolute sum of the difference track "
                    "(+1 and -1 at one word cancel there, so the true count is a little higher)")
     print(json.dumps(res))
