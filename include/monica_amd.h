@@ -210,6 +210,11 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   a reach outside 1 .. the window              mnc_linkage_phase_window: MNC_ERR_ARG
  *   a table with a negative count, or a count    mnc_linkage_add_tables: MNC_ERR_ARG, the accumulator untouched, the message
  *   in a cell past its contig's last site        names the cell
+ *   haplos after a call that ran both passes;    mnc_engine_add_haplos: MNC_ERR_UNSUPPORTED / MNC_ERR_ARG as for linkage, the
+ *   under MNC_CONTRACT_CHAIN                     accumulator untouched
+ *   k outside 2 .. 6, a '+' site, an unsorted    mnc_haplos_create: MNC_ERR_ARG (a row holds 2^k words; the list's rules are
+ *   list                                         mnc_linkage_create's)
+ *   2^31 or more records in one window           outside the contract: every word of mnc_haplos holds int32
  *   haplotags after a call that ran both the     mnc_engine_add_haplotag: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
  *   usual and the wide pass; under               linkage); MNC_ERR_ARG under MNC_CONTRACT_CHAIN (no CIGAR to take the columns
  *   MNC_CONTRACT_CHAIN                           from)
@@ -823,6 +828,73 @@ int  mnc_linkage_add_tables(mnc_linkage *lk, const int32_t *site /* [n_sites][2]
 /* The raw additive words (device pointers, laid out as above; either may be NULL), for a collective of the caller's.  Ordered
  * behind the adds only after a read-out call or a sync of the engines that added. */
 int  mnc_linkage_device(mnc_linkage *lk, const int32_t **d_site, const int32_t **d_pair);
+
+/* ---------------------------------------------------------------- haplos
+ * Local haplotypes: how often the reads spell each allele pattern over k CONSECUTIVE sites.  The pair tables answer "do
+ * these two alleles travel together"; four non-empty cells at a pair mean "three haplotypes or noise", and pairs at
+ * different distances cannot be combined into a count.  A read that crosses k neighbouring sites carries the whole string:
+ * two strains leave two frequent patterns in every window, three strains three wherever their differences interleave, and
+ * the frequencies are the strain ratios.  An mnc_haplos is an accumulator like mnc_linkage, with its lifetime, threading and
+ * cost rules: one index, one device, added to from the last batch as it stands in HBM on the engine's stream with no host
+ * wait (csrc/k_haplos.hip); reset and the read-outs are for one thread at a time; a batch that does not ask costs nothing.
+ * Integer arithmetic throughout.
+ *
+ * Sites: the list mnc_linkage_create takes, under the same checks and with the same messages.  k is 2 .. MNC_HAPLOS_MAX_K.
+ * Window i is the sites i, i + 1, .., i + k - 1; it exists iff all k lie on one contig.  Records are selected by `what`
+ * exactly as mnc_engine_add_linkage selects them, and what a record says at a site (REF, ALT, nothing) is the linkage
+ * section's rule, unchanged.  A record SPELLS window i iff it makes a statement at every one of the k sites; its pattern is
+ * the k statements read as a binary number, first site first: p = sum over t of a[i + t] << (k - 1 - t), REF = 0, ALT = 1
+ * (for k = 2 the pair cell 2 * a_i + a_j).  What is accumulated, int32:
+ *   hap[n_sites][1 << k]   hap[i][p] = the RECORDS that spelled window i as p (two records of one read are two records).
+ *                          Rows of sites with fewer than k - 1 successors on their contig stay zero.
+ * Addition commutes over order and batch cuts.  A consequence: a window that holds two alleles of one position is spelled
+ * only by records that are REF at that position -- a record with one of the alleles says nothing at the other site.
+ *
+ * Storage (what mnc_haplos_device hands out): ((1 << k) + 1) * n_sites words, first row[n_sites][1 << k], then a difference
+ * track[n_sites].  Per record whose range of sites [s_lo, s_hi) holds at least k, the windows inside it are the run
+ * [s_lo, s_hi - k + 1) of i: +1 at its first i, -1 one past its last.  A window of the run costs one atomic only where it
+ * is not all-REF: on word 0 of its row ("missing") where some site has no statement, else on word p.  The all-REF cell is
+ * derived:   hap[i][0] = (track[0] + .. + track[i]) - (row[i][0] + .. + row[i][(1 << k) - 1])
+ * Every word is additive, the differences included: ranks sum them with one collective of their own. */
+typedef struct mnc_haplos mnc_haplos;
+#define MNC_HAPLOS_MAX_K 6
+typedef struct {
+	int32_t window;                          /* i: the window's first site */
+	int32_t pattern;                         /* p */
+	int32_t count;                           /* hap[i][p] */
+	int32_t total;                           /* the sum of hap[i][] */
+} mnc_haplo_t;                               /* 16 bytes */
+/* MNC_ERR_ARG, before any device is looked at: a NULL pointer; k outside 2 .. MNC_HAPLOS_MAX_K; whatever
+ * mnc_linkage_create refuses in a site list, with its messages.  MNC_ERR_NODEVICE without a gfx950 device, MNC_ERR_NOMEM
+ * when 4 * 2^k + 27 bytes per site do not fit the HBM that is free. */
+int  mnc_haplos_create(mnc_index *idx, int device, const mnc_variant_t *sites, int64_t n_sites, int32_t k, mnc_haplos **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_haplos_free(mnc_haplos *hp);
+/* clears every word (the site list stays); asynchronous */
+int  mnc_haplos_reset(mnc_haplos *hp);
+/* HBM the accumulator holds: 4 * 2^k + 4 bytes per site of words, 9 of the list, 13 of the read-outs' scratch and 2^k / 64 of
+ * the call's tiles */
+int  mnc_haplos_device_bytes(const mnc_haplos *hp, int64_t *bytes);
+/* Adds the last classified batch of `eng`; answers as mnc_engine_add_linkage answers in the same situations, the accumulator
+ * untouched on any error.  Asynchronous on the engine's stream, no host wait. */
+int  mnc_engine_add_haplos(mnc_engine *eng, mnc_haplos *hp, int what);
+/* Rows [first, first + n) of hap[][] with cell 0 derived (MNC_ERR_ARG outside the list).  Waits for the work queued so far
+ * and leaves the accumulator as it is. */
+int  mnc_haplos_fetch(mnc_haplos *hp, int64_t first, int64_t n, int32_t *out /* [n][1 << k] */);
+/* How many haplotypes each window shows, on the device -- count, scan, place -- so only the answer travels.  total[i] = the
+ * sum of hap[i][]; window i is JUDGED iff total[i] >= min_total and total[i] > 0; in a judged window pattern p is CALLED iff
+ * hap[i][p] >= min_count and hap[i][p] * 1000 >= min_permille * total[i] (int64).  n_haps[i] = the called patterns, 0 for a
+ * window that is not judged.  hist[c][h] = the judged windows of contig c with n_haps == h for h = 0 .. 6, slot 7 those with
+ * n_haps >= 7: with the caller's thresholds, the largest h with a substantial hist[c][h] is the least number of strains of
+ * contig c in the sample.  out receives one record per called pattern in (window, pattern) order, *n their number.  Any
+ * output may be NULL.  When out or n is given and cap is below the number of records: MNC_ERR_RANGE, *n set, nothing
+ * written (as mnc_pileup_call_variants); with out NULL and cap sufficient the records are left out.  Waits and threading
+ * as mnc_haplos_fetch. */
+int  mnc_haplos_call(mnc_haplos *hp, int32_t min_total, int32_t min_count, int32_t min_permille, uint8_t *n_haps /* [n_sites] */,
+                     int32_t *total /* [n_sites] */, int64_t *hist /* [n_contigs][8] */, mnc_haplo_t *out, int64_t cap, int64_t *n);
+/* The raw additive words (a device pointer, laid out as above; may be NULL), for a collective of the caller's.  Ordered
+ * behind the adds only after a read-out call or a sync of the engines that added. */
+int  mnc_haplos_device(mnc_haplos *hp, const int32_t **d_words);
 
 /* ---------------------------------------------------------------- haplotag
  * Which READS belong to which side of a phase block, and how many.  mnc_linkage_phase ends at block[] / phase[]: it says

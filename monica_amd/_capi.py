@@ -101,6 +101,8 @@ EXPORTS = [
     "mnc_linkage_create", "mnc_linkage_free", "mnc_linkage_reset", "mnc_linkage_device_bytes", "mnc_engine_add_linkage",
     "mnc_linkage_fetch_sites", "mnc_linkage_fetch_pairs", "mnc_linkage_phase", "mnc_linkage_device",
     "mnc_linkage_phase_window", "mnc_linkage_add_tables",
+    "mnc_haplos_create", "mnc_haplos_free", "mnc_haplos_reset", "mnc_haplos_device_bytes", "mnc_engine_add_haplos",
+    "mnc_haplos_fetch", "mnc_haplos_call", "mnc_haplos_device",
     "mnc_haplotag_create", "mnc_haplotag_free", "mnc_haplotag_reset", "mnc_haplotag_device_bytes", "mnc_haplotag_n_blocks",
     "mnc_engine_add_haplotag", "mnc_haplotag_fetch_blocks", "mnc_haplotag_fetch_tags", "mnc_haplotag_device",
     "mnc_engine_add_pileup_phased",
@@ -279,6 +281,14 @@ def lib():
     sig("mnc_linkage_device", i32, [vp, pp, pp])
     sig("mnc_linkage_phase_window", i32, [vp, i32, i32, i32, vp, vp, C.POINTER(i64)])
     sig("mnc_linkage_add_tables", i32, [vp, vp, vp])
+    sig("mnc_haplos_create", i32, [vp, i32, vp, i64, i32, pp])
+    sig("mnc_haplos_free", None, [vp])
+    sig("mnc_haplos_reset", i32, [vp])
+    sig("mnc_haplos_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_engine_add_haplos", i32, [vp, vp, i32])
+    sig("mnc_haplos_fetch", i32, [vp, i64, i64, vp])
+    sig("mnc_haplos_call", i32, [vp, i32, i32, i32, vp, vp, vp, vp, i64, C.POINTER(i64)])
+    sig("mnc_haplos_device", i32, [vp, pp])
     sig("mnc_haplotag_create", i32, [vp, i32, vp, i64, vp, vp, i64, i32, i32, pp])
     sig("mnc_haplotag_free", None, [vp])
     sig("mnc_haplotag_reset", i32, [vp])
@@ -665,6 +675,11 @@ class Engine:
         `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
         self._add("mnc_engine_add_linkage", linkage, int(what))
 
+    def add_haplos(self, haplos, what=COV_GATED):
+        """`mnc_engine_add_haplos`: add the last classified batch, as it stands in HBM, to the accumulator `haplos`.
+        Asynchronous; `what` is one selector, as for `add_linkage`."""
+        self._add("mnc_engine_add_haplos", haplos, int(what))
+
     def add_haplotag(self, haplotag, what=COV_GATED):
         """`mnc_engine_add_haplotag`: add the last classified batch, as it stands in HBM, to the accumulator `haplotag` and
         write its reads' tags.  `what` is one of COV_GATED / COV_PRIMARY / COV_ALL / COV_ASSIGNED.  Asynchronous."""
@@ -1034,6 +1049,56 @@ class Linkage(_Accumulator):
         a, b = C.c_void_p(), C.c_void_p()
         check(lib().mnc_linkage_device(self._h, C.byref(a), C.byref(b)))
         return int(a.value or 0), int(b.value or 0)
+
+
+# ---------------------------------------------------------------------------------- haplos
+HAPLOS_MAX_K = 6
+HAPLO_DTYPE = np.dtype([("window", "<i4"), ("pattern", "<i4"), ("count", "<i4"), ("total", "<i4")])
+
+
+class Haplos(_Accumulator):
+    """Owner of an ``mnc_haplos``: per window of `k` consecutive sites of a fixed list (`sites` as `Linkage` takes them) how
+    many records spelled each of the 2^k allele patterns, first site first, REF 0 and ALT 1 -- accumulated from batch to
+    batch by `Engine.add_haplos` (include/monica_amd.h, "haplos").  `call()` counts the patterns that pass the thresholds
+    per window, on the device: two strains show two, three strains three wherever their differences interleave."""
+
+    _c = "haplos"
+
+    def __init__(self, index, sites, k=4, device=0):
+        self.index = index
+        self.sites = np.ascontiguousarray(sites, dtype=VARIANT_DTYPE)
+        self.k = int(k)
+        self._room = len(self.sites)                            # records `call()` makes room for
+        self._create(index, device, self.sites.ctypes.data if len(self.sites) else None, len(self.sites), self.k)
+
+    def table(self, first=0, n=None):
+        """int32[n, 2^k]: hap[i][p] of windows [first, first + n) (to the end by default), window i the sites i .. i + k - 1."""
+        n = len(self.sites) - int(first) if n is None else int(n)
+        out = np.zeros((max(n, 0), 1 << self.k), dtype=np.int32)
+        check(lib().mnc_haplos_fetch(self._h, int(first), n, out.ctypes.data if out.size else None))
+        return out
+
+    def call(self, min_total=1, min_count=1, min_permille=0):
+        """`mnc_haplos_call`: (n_haps uint8[n_sites], total int32[n_sites], hist int64[n_contigs, 8], records (HAPLO_DTYPE) in
+        (window, pattern) order).  One C call with room for as many records as the last call found (at first: one per window); a
+        second one only when that is short."""
+        thr, n, ns = (int(min_total), int(min_count), int(min_permille)), C.c_int64(0), len(self.sites)
+        n_haps, total = np.zeros(ns, dtype=np.uint8), np.zeros(ns, dtype=np.int32)
+        hist, out = np.zeros((len(self.index.contig_lens), 8), dtype=np.int64), np.empty(self._room, dtype=HAPLO_DTYPE)
+        while True:
+            rc = lib().mnc_haplos_call(self._h, *thr, n_haps.ctypes.data if ns else None, total.ctypes.data if ns else None,
+                                       hist.ctypes.data if hist.size else None, out.ctypes.data if len(out) else None, len(out), C.byref(n))
+            if rc != ERR_RANGE:
+                check(rc)
+                self._room = n.value
+                return n_haps, total, hist, out[:n.value]
+            out = np.empty(n.value, dtype=HAPLO_DTYPE)              # nothing was written: once more, with room
+
+    def device(self):
+        """Device address of the (2^k + 1) * n_sites raw words, the rows and the difference track: `mnc_haplos_device`."""
+        a = C.c_void_p()
+        check(lib().mnc_haplos_device(self._h, C.byref(a)))
+        return int(a.value or 0)
 
 
 # ---------------------------------------------------------------------------------- haplotag

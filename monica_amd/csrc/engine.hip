@@ -108,6 +108,8 @@ int pileup_min_qual(const mnc_pileup *pu);
 int abundance_add(mnc_abundance *ab, const Batch &B, hipStream_t st);
 const Accum *as_accum(const mnc_linkage *lk);               // k_linkage.hip
 int linkage_add(mnc_linkage *lk, const Batch &B, int sel, hipStream_t st);
+const Accum *as_accum(const mnc_haplos *hp);                // k_haplos.hip
+int haplos_add(mnc_haplos *hp, const Batch &B, int sel, hipStream_t st);
 const Accum *as_accum(const mnc_haplotag *ht);              // k_haplotag.hip
 int haplotag_fits(const mnc_haplotag *ht, const Batch &B);
 int haplotag_add(mnc_haplotag *ht, const Batch &B, int sel, hipStream_t st);
@@ -1806,6 +1808,19 @@ extern "C" int mnc_engine_add_linkage(mnc_engine *e, mnc_linkage *lk, int what)
 	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
 	return linkage_add(lk, e->B, sel, e->stream);
+}
+
+// ---------------------------------------------------------------- local haplotypes of the last batch
+// The same for the pattern counts over k consecutive sites (k_haplos.hip): linkage's checks, one kernel on the engine's stream.
+extern "C" int mnc_engine_add_haplos(mnc_engine *e, mnc_haplos *hp, int what)
+{
+	if (!e || !hp) return MNC_ERR_ARG;
+	int sel = 0;
+	if (int rc = add_selector(what, true, &sel)) return rc;
+	if (int rc = add_precheck(e, as_accum(hp), "haplos", "haplos need the CIGARs of MNC_CONTRACT_DP")) return rc;
+	if (e->B.n_reads == 0) return MNC_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return haplos_add(hp, e->B, sel, e->stream);
 }
 
 // ---------------------------------------------------------------- haplotags of the last batch

@@ -343,6 +343,11 @@ class Aligner:
         index on this object's device: pass it to `map_batch` in a second pass over the reads, then `phase()` it."""
         return _capi.Linkage(self._index, sites, window, self._device)
 
+    def haplos(self, sites, k=4):
+        """A local-haplotype accumulator (`_capi.Haplos`) over `sites` (as `linkage()` takes them) for this index on this
+        object's device: pass it to `map_batch`, then read `table()` and `call()`."""
+        return _capi.Haplos(self._index, sites, k, self._device)
+
     def haplotag(self, sites, block, phase, cap_reads, min_votes=2, min_permille=600, keep=None):
         """A haplotag accumulator (`_capi.Haplotag`) over `sites` with the `block` / `phase` that `linkage().phase()` gave, for
         batches of at most `cap_reads` reads: pass it to `map_batch` in a third pass, then read `blocks()` and `tags()`.
@@ -369,7 +374,8 @@ class Aligner:
 
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
                   abundance=None, quals=None, linkage=None, linkage_what=_capi.COV_GATED,
-                  haplotag=None, haplotag_what=_capi.COV_GATED, phased=None, phased_what=_capi.COV_GATED):
+                  haplotag=None, haplotag_what=_capi.COV_GATED, phased=None, phased_what=_capi.COV_GATED,
+                  haplos=None, haplos_what=_capi.COV_GATED):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
@@ -380,7 +386,8 @@ class Aligner:
         `linkage()`) the batch is added to it, `linkage_what` one selector; with `haplotag` (an accumulator of `haplotag()`)
         likewise, `haplotag_what` one selector, and its `tags()` are this batch's; with `phased` = (haplotag, hap0, hap1,
         rest or None) -- an accumulator of `haplotag()` and pileups of `pileup()` -- the batch's columns are added to the
-        pileup of the haplotype their record is decided for (`Engine.add_pileup_phased`), `phased_what` one selector."""
+        pileup of the haplotype their record is decided for (`Engine.add_pileup_phased`), `phased_what` one selector; with
+        `haplos` (an accumulator of `haplos()`) the batch is added to it, `haplos_what` one selector."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -401,6 +408,8 @@ class Aligner:
             eng.add_haplotag(haplotag, haplotag_what)
         if phased is not None:
             eng.add_pileup_phased(*phased, what=phased_what)
+        if haplos is not None:
+            eng.add_haplos(haplos, haplos_what)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
