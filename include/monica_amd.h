@@ -236,6 +236,16 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   both the usual and the wide pass             mnc_engine_add_abundance); MNC_ERR_ARG under MNC_CONTRACT_CHAIN
  *   a read with more than `width` candidates     the `width` ranked highest stay (score descending, ties to the smaller genome
  *   within max_delta, over all parts             id); the read is counted in n_truncated_reads of mnc_carry_info
+ *   lca after a call that ran both the usual     mnc_engine_add_lca: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
+ *   and the wide pass; under MNC_CONTRACT_CHAIN  mnc_engine_add_abundance); MNC_ERR_ARG under MNC_CONTRACT_CHAIN (no dp_max)
+ *   a batch, or rows of a carry, beyond          mnc_engine_add_lca, mnc_lca_add_carry: MNC_ERR_RANGE, the accumulator untouched
+ *   cap_reads                                    (the node store is allocated once, at creation)
+ *   a taxonomy deeper than MNC_LCA_MAX_DEPTH =   mnc_lca_create: MNC_ERR_ARG, the message names the node (a leaf's ancestor
+ *   64 levels, with a cycle, with no root or two line fits one wave's lanes)
+ *   a taxonomy of more than MNC_LCA_LDS_NODES =  exact; the add reads the tree through L2 and counts with one global atomic
+ *   4 096 nodes                                  per read, where a smaller tree and its counts sit in LDS
+ *   nodes of an earlier add, or of two engines   not kept: node[] is the most recent add's (one mnc_lca per engine; the
+ *   adding to one mnc_lca                        direct counts sum)
  */
 
 /* ---------------------------------------------------------------- classify
@@ -1167,6 +1177,69 @@ int  mnc_abundance_create_global(int device, int32_t n_genomes, int64_t cap_cand
  * wait, for the carry's merges).  MNC_ERR_RANGE: first_read + n_reads > cap_reads.  The add itself is asynchronous on the
  * accumulator's stream behind the carry's merges.  The carry is left as it is. */
 int  mnc_abundance_add_carry(mnc_abundance *ab, mnc_carry *cc, int64_t first_read, int64_t n_reads);
+
+/* ---------------------------------------------------------------- lca
+ * Placing ambiguous reads on a taxonomy.  A read is classified only when it has a primary hit with mapq >= min_mapq; two
+ * strains of one species agree on most of their length, so reads from the shared stretches get a low MAPQ and count for
+ * nobody.  An mnc_lca places every read on the LOWEST node of the caller's taxonomy that covers all of the read's candidate
+ * genomes -- the species, or the genus -- as Kraken, Centrifuge and MEGAN do, and counts the reads per node.  It is an
+ * accumulator like mnc_abundance, with its lifetime, threading and cost rules: added to from the last batch as it stands in
+ * HBM on the engine's stream with no host wait (csrc/k_lca.hip); engines of the same index and device may add from their own
+ * threads; reset and the read-outs are for one thread at a time; a batch that does not ask costs nothing.  Integer
+ * arithmetic throughout.
+ *
+ * The taxonomy: parent[n_nodes], int32.  Nodes 0 .. n_genomes - 1 are the index's genomes in mnc_index_contig_genome order
+ * (for a global accumulator: the genomes of the whole database in part order); the nodes from n_genomes on are the caller's
+ * inner nodes.  Exactly one node has parent -1, the root.  A genome node may have children.  A node lies at most
+ * MNC_LCA_MAX_DEPTH levels deep, the root included.
+ *
+ * Candidates: the abundance's, exactly ("What one read contributes").  Of the records mnc_engine_add_abundance counts,
+ * s_g = the largest dp_max on genome g, best = the largest s_g, and g is a candidate iff best - s_g <= max_delta.  The
+ * read's node is the LCA of its candidates: the genome's own node for one candidate, -1 for a read with no counted record.
+ *
+ * What an add does, per read r of the batch: node[r] (int32) is written, direct[node] (int64) grows by one, and n_placed or
+ * n_unplaced grows.  direct[] is additive over batches, engines and ranks; node[] is the latest add's, as the haplotag's
+ * tags are.  Reads are counted, not bases: a weighting is one bincount over node[] for the caller. */
+typedef struct mnc_lca mnc_lca;
+#define MNC_LCA_MAX_DEPTH 64                 /* levels of the taxonomy, the root included: a leaf's line fits one wave's lanes */
+#define MNC_LCA_LDS_NODES 4096               /* the largest taxonomy the add kernel holds in LDS with its counts (16 bytes a node) */
+/* idx: the index whose genomes are the nodes 0 .. n_genomes - 1 (n_genomes must be its number of genomes), or NULL for a
+ * global accumulator as mnc_abundance_create_global makes one: mnc_engine_add_lca answers MNC_ERR_ARG for it,
+ * mnc_lca_add_carry fills it.  MNC_ERR_ARG, before any device is looked at and with a message that names the node:
+ * n_nodes < n_genomes; a parent outside -1 .. n_nodes - 1; no root, or a second one; a node that is its own ancestor; a
+ * node deeper than MNC_LCA_MAX_DEPTH; also max_delta < 0 and cap_reads outside 1 .. 2^31 - 1.  MNC_ERR_NODEVICE without a
+ * gfx950 device, MNC_ERR_NOMEM when 44 bytes per node and 4 per read do not fit the HBM that is free.  The Python layer's
+ * default: max_delta = 80. */
+int  mnc_lca_create(mnc_index *idx_or_null, int device, int32_t n_genomes, const int32_t *parent, int32_t n_nodes,
+                    int32_t max_delta, int64_t cap_reads, mnc_lca **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_lca_free(mnc_lca *lca);
+/* every count zero, every node -1 (the taxonomy stays); asynchronous */
+int  mnc_lca_reset(mnc_lca *lca);
+/* HBM the accumulator holds */
+int  mnc_lca_device_bytes(const mnc_lca *lca, int64_t *bytes);
+/* the counts as they stand (waits for the adds queued so far); any pointer may be NULL.  n_truncated: the carry rows added
+ * whose truncated bit was set */
+int  mnc_lca_info(mnc_lca *lca, int64_t *n_placed, int64_t *n_unplaced, int64_t *n_truncated);
+/* Adds the last classified batch of `eng` and writes node[0 .. n_reads).  Asynchronous on the engine's stream, no host wait.
+ * Errors as for mnc_engine_add_abundance -- MNC_ERR_ARG: another index or device, a global accumulator, no batch classified
+ * yet, MNC_CONTRACT_CHAIN; MNC_ERR_UNSUPPORTED after a call that ran both passes -- and MNC_ERR_RANGE when the batch holds
+ * more than cap_reads reads.  The accumulator is untouched on any error. */
+int  mnc_engine_add_lca(mnc_engine *eng, mnc_lca *lca);
+/* The carry's rows first_read .. first_read + n_reads - 1, each as one read, under mnc_abundance_add_carry's ordering and
+ * checks: MNC_ERR_ARG when the carry's max_delta or device differs or it holds a genome id >= n_genomes (read back first: the
+ * one host wait); MNC_ERR_RANGE beyond the carry's or the accumulator's cap_reads.  Writes node[first_read + r].  A row that
+ * holds no pair is unplaced; a truncated row is placed by what it holds and counted in n_truncated.  The carry is left as
+ * it is. */
+int  mnc_lca_add_carry(mnc_lca *lca, mnc_carry *carry, int64_t first_read, int64_t n_reads);
+/* direct[v] = the reads placed on node v itself; clade[v] = the sum of direct over v's subtree (computed on the device: direct
+ * in pre-order, one exclusive scan, a difference per node).  Either pointer may be NULL.  Waits. */
+int  mnc_lca_fetch(mnc_lca *lca, int64_t *direct /* [n_nodes] */, int64_t *clade /* [n_nodes] */);
+/* node[first .. first + n) of the latest add (MNC_ERR_ARG outside cap_reads); -1 for a read without a node.  Waits. */
+int  mnc_lca_fetch_nodes(mnc_lca *lca, int64_t first, int64_t n, int32_t *out);
+/* The raw additive words direct[n_nodes] and the node store node[cap_reads] (device pointers; either may be NULL), for a
+ * collective of the caller's.  Ordered behind the adds only after a read-out call or a sync of the engines that added. */
+int  mnc_lca_device(mnc_lca *lca, const int64_t **d_direct, const int32_t **d_node);
 
 /* ---------------------------------------------------------------- FASTQ batches and read routing
  * Replaces the per-record Biopython objects of the reference's loop:

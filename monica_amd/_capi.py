@@ -111,6 +111,8 @@ EXPORTS = [
     "mnc_abundance_device", "mnc_abundance_create_global", "mnc_abundance_add_carry",
     "mnc_carry_create", "mnc_carry_free", "mnc_carry_reset", "mnc_carry_reserve", "mnc_carry_device_bytes", "mnc_engine_carry_candidates",
     "mnc_carry_add_lists", "mnc_carry_merge", "mnc_carry_info", "mnc_carry_fetch", "mnc_carry_device",
+    "mnc_lca_create", "mnc_lca_free", "mnc_lca_reset", "mnc_lca_device_bytes", "mnc_lca_info", "mnc_engine_add_lca",
+    "mnc_lca_add_carry", "mnc_lca_fetch", "mnc_lca_fetch_nodes", "mnc_lca_device",
 ]
 
 
@@ -323,6 +325,16 @@ def lib():
     sig("mnc_carry_info", i32, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)])
     sig("mnc_carry_fetch", i32, [vp, i64, i64, vp, vp, vp, vp])
     sig("mnc_carry_device", i32, [vp, pp, pp, C.POINTER(i64), C.POINTER(C.c_int32)])
+    sig("mnc_lca_create", i32, [vp, i32, C.c_int32, vp, C.c_int32, C.c_int32, i64, pp])
+    sig("mnc_lca_free", None, [vp])
+    sig("mnc_lca_reset", i32, [vp])
+    sig("mnc_lca_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_lca_info", i32, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)])
+    sig("mnc_engine_add_lca", i32, [vp, vp])
+    sig("mnc_lca_add_carry", i32, [vp, vp, i64, i64])
+    sig("mnc_lca_fetch", i32, [vp, vp, vp])
+    sig("mnc_lca_fetch_nodes", i32, [vp, i64, i64, vp])
+    sig("mnc_lca_device", i32, [vp, pp, pp])
     _LIB = L
     return L
 
@@ -703,6 +715,12 @@ class Engine:
         """`mnc_engine_carry_candidates`: merge the candidate genomes of every read of the last classified batch into the
         rows `first_read ..` of `carry`; genome g of this engine's index is genome `genome_offset` + g there.  Asynchronous."""
         self._add("mnc_engine_carry_candidates", carry, int(first_read), int(genome_offset))
+
+    def add_lca(self, lca):
+        """`mnc_engine_add_lca`: place every read of the last classified batch, as it stands in HBM, on the lowest common
+        ancestor of its candidate genomes in the taxonomy of `lca`, and write the reads' nodes.  Asynchronous."""
+        self._add("mnc_engine_add_lca", lca)
+        lca.n_reads = self.n_reads
 
     def _add(self, symbol, acc, *args):
         check(getattr(lib(), symbol)(self._h, acc._h if acc is not None else None, *args))
@@ -1324,6 +1342,91 @@ class Carry(_Accumulator):
         h, s, n, w = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int32(0)
         check(lib().mnc_carry_device(self._h, C.byref(h), C.byref(s), C.byref(n), C.byref(w)))
         return int(h.value or 0), int(s.value or 0), int(n.value), int(w.value)
+
+
+# ---------------------------------------------------------------------------------- lca
+LCA_MAX_DEPTH = 64                      # MNC_LCA_MAX_DEPTH: levels of a taxonomy, the root included
+LCA_LDS_NODES = 4096                    # MNC_LCA_LDS_NODES: the largest taxonomy the add kernel holds in LDS
+LCA_CAP_READS = 1 << 20                 # reads per add when the caller names none (the most one classify call takes): 4 MiB of HBM
+
+
+def taxonomy_from_names(genome_names):
+    """monica's own two ranks from genome names of the form ``Genus_species:accession``: genome -> tax_unit (the text before
+    ':') -> genus (its text before '_') -> root.  Returns (parent int32[n_nodes], node_names): nodes 0 .. G - 1 are the
+    genomes, the inner nodes follow in the order in which a walk up from genome 0, 1, .. first meets them."""
+    names = list(genome_names)
+    parent, ids = [-1] * len(names), {}
+
+    def inner(key, name):
+        if key not in ids:
+            ids[key] = len(names)
+            names.append(name), parent.append(-1)
+        return ids[key]
+
+    for g, name in enumerate(genome_names):
+        tax_unit = name.split(":")[0]
+        genus = tax_unit.split("_")[0]
+        t, s, root = inner(("tax_unit", tax_unit), tax_unit), inner(("genus", genus), genus), inner(("root",), "root")
+        parent[g], parent[t], parent[s] = t, s, root
+    if not ids:
+        inner(("root",), "root")
+    return np.array(parent, dtype=np.int32), names
+
+
+class Lca(_Accumulator):
+    """Owner of an ``mnc_lca``: every read placed on the lowest node of the taxonomy `parent` that covers all of its
+    candidate genomes (the abundance's candidates, within `max_delta` of the read's best), the reads counted per node from
+    batch to batch by `Engine.add_lca`, and per read of the latest add its node (include/monica_amd.h, "lca").  Nodes
+    0 .. G - 1 of `parent` are the genomes of `index`; with `index` None the accumulator is global -- `n_genomes` genomes
+    of a whole database in part order -- and is filled by `add_carry`.  `cap_reads`: the most reads an add may hold."""
+
+    _c = "lca"
+
+    def __init__(self, index, parent, n_genomes=None, max_delta=ABUNDANCE_MAX_DELTA, cap_reads=LCA_CAP_READS, device=0):
+        self.index = index
+        self.parent = np.ascontiguousarray(parent, dtype=np.int32)
+        if self.parent.ndim != 1:
+            raise ValueError("parent holds one entry per node")
+        if n_genomes is None:
+            if index is None:
+                raise ValueError("a global accumulator (no index) needs n_genomes")
+            n_genomes = len(index.genome_names)
+        self.n_genomes, self.n_nodes, self.max_delta, self.device_id = int(n_genomes), len(self.parent), int(max_delta), int(device)
+        self.n_reads = 0                                        # of the latest add (Engine.add_lca, add_carry)
+        self._create(index, device, self.n_genomes, self.parent.ctypes.data if self.n_nodes else None, self.n_nodes, self.max_delta, int(cap_reads))
+
+    def info(self):
+        """{"n_placed", "n_unplaced", "n_truncated"} as they stand (waits for the adds queued so far)."""
+        v = [C.c_int64(0) for _ in range(3)]
+        check(lib().mnc_lca_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_placed", "n_unplaced", "n_truncated"), (int(x.value) for x in v)))
+
+    def counts(self):
+        """(direct int64[n_nodes], clade int64[n_nodes]): the reads placed on each node itself, and in its subtree."""
+        direct, clade = np.zeros(self.n_nodes, dtype=np.int64), np.zeros(self.n_nodes, dtype=np.int64)
+        check(lib().mnc_lca_fetch(self._h, direct.ctypes.data, clade.ctypes.data))
+        return direct, clade
+
+    def nodes(self, first=0, n=None):
+        """int32[n]: the nodes of reads [first, first + n) of the latest add (to its end by default); -1 for a read without one."""
+        n = self.n_reads - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=np.int32)
+        check(lib().mnc_lca_fetch_nodes(self._h, int(first), n, out.ctypes.data if out.size else None))
+        return out
+
+    def add_carry(self, carry, first_read=0, n_reads=None):
+        """`mnc_lca_add_carry`: rows `first_read .. first_read + n_reads - 1` of the candidate carry `carry` (default: to
+        its end), each as one read; read r's node is `nodes()[first_read + r]`.  The carry is left as it is."""
+        if n_reads is None:
+            n_reads = carry.info()["cap_reads"] - int(first_read)
+        check(lib().mnc_lca_add_carry(self._h, carry._h if carry is not None else None, int(first_read), int(n_reads)))
+        self.n_reads = int(first_read) + int(n_reads)
+
+    def device(self):
+        """(device address of direct[n_nodes], of node[cap_reads]): `mnc_lca_device`."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().mnc_lca_device(self._h, C.byref(a), C.byref(b)))
+        return int(a.value or 0), int(b.value or 0)
 
 
 # ---------------------------------------------------------------------------------- host helpers

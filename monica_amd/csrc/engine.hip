@@ -118,6 +118,9 @@ int pile_phase_add(const mnc_haplotag *ht, mnc_pileup *hap0, mnc_pileup *hap1, m
 // the candidate carry (k_carry.hip): an Accum of a device, of no index
 const Accum *as_accum(const mnc_carry *cc);
 int carry_add(mnc_carry *cc, const Batch &B, int n_contigs, int n_genomes, int64_t first_read, int32_t genome_offset, hipStream_t st);
+const Accum *as_accum(const mnc_lca *lc);                   // k_lca.hip
+int lca_fits(const mnc_lca *lc, const Batch &B);
+int lca_add(mnc_lca *lc, const Batch &B, hipStream_t st);
 
 // ---------------------------------------------------------------- run offsets of the partition
 // The sketch writes one histogram row per tile ([tile][bucket]); the query records are laid out
@@ -1890,6 +1893,18 @@ extern "C" int mnc_engine_add_abundance(mnc_engine *e, mnc_abundance *ab)
 	if (e->B.n_reads == 0) return MNC_OK;
 	HIP_TRY(hipSetDevice(e->device));
 	return abundance_add(ab, e->B, e->stream);
+}
+
+// ---------------------------------------------------------------- taxonomic placement of the last batch
+// The same records placed on the lowest common ancestor of their genomes (k_lca.hip): abundance's checks, then the node
+// store's capacity; one kernel on the engine's stream.  An empty batch is an add of no reads.  A global accumulator is of no
+// index: MNC_ERR_ARG.
+extern "C" int mnc_engine_add_lca(mnc_engine *e, mnc_lca *lc)
+{
+	if (int rc = add_precheck(e, as_accum(lc), "taxonomic placements", "taxonomic placements need the dp_max of MNC_CONTRACT_DP")) return rc;
+	if (int rc = lca_fits(lc, e->B)) return rc;
+	HIP_TRY(hipSetDevice(e->device));
+	return lca_add(lc, e->B, e->stream);
 }
 
 // ---------------------------------------------------------------- candidates of the last batch, carried across index parts

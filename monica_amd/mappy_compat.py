@@ -372,10 +372,21 @@ class Aligner:
         """An abundance accumulator for the genomes of a whole database (`_capi.Abundance.global_`) on this object's device."""
         return _capi.Abundance.global_(self._device, len(genome_names), cap_cands, max_delta, scale_q, genome_names=genome_names)
 
+    def lca(self, parent=None, max_delta=_capi.ABUNDANCE_MAX_DELTA, cap_reads=_capi.LCA_CAP_READS):
+        """A lowest-common-ancestor accumulator (`_capi.Lca`) for this index on this object's device: pass it to `map_batch`,
+        then read `nodes()` and `counts()`.  `parent`: the taxonomy, nodes 0 .. G - 1 the index's genomes; None: monica's own
+        two ranks from the genome names (`_capi.taxonomy_from_names`), whose node names are then in `.node_names`."""
+        node_names = None
+        if parent is None:
+            parent, node_names = _capi.taxonomy_from_names(self._index.genome_names)
+        acc = _capi.Lca(self._index, parent, max_delta=max_delta, cap_reads=cap_reads, device=self._device)
+        acc.node_names = node_names
+        return acc
+
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
                   abundance=None, quals=None, linkage=None, linkage_what=_capi.COV_GATED,
                   haplotag=None, haplotag_what=_capi.COV_GATED, phased=None, phased_what=_capi.COV_GATED,
-                  haplos=None, haplos_what=_capi.COV_GATED):
+                  haplos=None, haplos_what=_capi.COV_GATED, lca=None):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
@@ -387,7 +398,8 @@ class Aligner:
         likewise, `haplotag_what` one selector, and its `tags()` are this batch's; with `phased` = (haplotag, hap0, hap1,
         rest or None) -- an accumulator of `haplotag()` and pileups of `pileup()` -- the batch's columns are added to the
         pileup of the haplotype their record is decided for (`Engine.add_pileup_phased`), `phased_what` one selector; with
-        `haplos` (an accumulator of `haplos()`) the batch is added to it, `haplos_what` one selector."""
+        `haplos` (an accumulator of `haplos()`) the batch is added to it, `haplos_what` one selector; with `lca` (an
+        accumulator of `lca()`) every read is placed on its taxonomy, and its `nodes()` are this batch's."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -410,6 +422,8 @@ class Aligner:
             eng.add_pileup_phased(*phased, what=phased_what)
         if haplos is not None:
             eng.add_haplos(haplos, haplos_what)
+        if lca is not None:
+            eng.add_lca(lca)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
