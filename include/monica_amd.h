@@ -246,6 +246,19 @@ int  mnc_engine_device_bytes(mnc_engine *eng, int64_t *bytes);         /* HBM he
  *   4 096 nodes                                  per read, where a smaller tree and its counts sit in LDS
  *   nodes of an earlier add, or of two engines   not kept: node[] is the most recent add's (one mnc_lca per engine; the
  *   adding to one mnc_lca                        direct counts sum)
+ *   more than MNC_DEMUX_MAX_BARCODES = 256       mnc_demux_create: MNC_ERR_ARG (a barcode's index is 8 bits of the key the lanes
+ *   barcodes, or none                            compare, and reads[] with its two extra words sits in LDS)
+ *   a barcode of more than MNC_DEMUX_MAX_LEN =   mnc_demux_create: MNC_ERR_ARG, the message names the barcode (a pattern is one
+ *   64 bases, an empty one, a character that is  64-bit word of the bit-vector search; up to 32 bases the 32-bit kernel runs);
+ *   none of ACGTU                                the message names the barcode and the position
+ *   a window outside 1 .. MNC_DEMUX_MAX_WINDOW   mnc_demux_create: MNC_ERR_ARG (a cut length is 11 bits of the same key; two
+ *   = 1 024                                      texts of a wave are 2 KiB of LDS)
+ *   demux after a call that ran both the usual   mnc_engine_add_demux: MNC_ERR_UNSUPPORTED, the accumulator untouched (as for
+ *   and the wide pass                            mnc_engine_add_coverage); both contracts serve
+ *   a batch beyond cap_reads                     mnc_engine_add_demux, mnc_demux_add: MNC_ERR_RANGE, the accumulator untouched
+ *   tags of an earlier add, or of two engines    not kept: the tags are the most recent add's, whole (the adds to one mnc_demux
+ *   adding to one mnc_demux                      run one behind the other on the device; one mnc_demux per engine keeps every
+ *                                                batch's tags; the counts sum either way)
  */
 
 /* ---------------------------------------------------------------- classify
@@ -1240,6 +1253,88 @@ int  mnc_lca_fetch_nodes(mnc_lca *lca, int64_t first, int64_t n, int32_t *out);
 /* The raw additive words direct[n_nodes] and the node store node[cap_reads] (device pointers; either may be NULL), for a
  * collective of the caller's.  Ordered behind the adds only after a read-out call or a sync of the engines that added. */
 int  mnc_lca_device(mnc_lca *lca, const int64_t **d_direct, const int32_t **d_node);
+
+/* ---------------------------------------------------------------- demux
+ * Which sample a read is from.  A barcoded run puts several samples on one flow cell: every read carries its sample's
+ * barcode near its front and, with ligation kits, the reverse complement of that barcode near its rear.  An mnc_demux
+ * searches every barcode of a caller's set in both ends of every read, approximately, on the device (csrc/k_demux.hip),
+ * decides the read's barcode, writes a tag per read and counts the reads per barcode -- and, per barcode, what mnc_counts
+ * counts per genome, so one stream of reads yields one taxon table per sample.  It is an accumulator like mnc_lca, with its
+ * lifetime, threading and cost rules: engines of the same index and device may add from their own threads; reset and the
+ * read-outs are for one thread at a time; a batch that does not ask costs nothing.  Integer arithmetic throughout.
+ * One difference: the adds to one mnc_demux are ORDERED on the device -- each waits for the one queued before it, whichever
+ * engine's stream it is on -- because an add's taxa are counted from the tags it has just written to the accumulator's one
+ * tag store.  The hosts' threads still do not wait; the counts are exact whatever the number of engines.
+ *
+ * Barcodes: n_barcodes patterns (1 .. MNC_DEMUX_MAX_BARCODES) of 1 .. MNC_DEMUX_MAX_LEN bases each, of any mix of lengths,
+ * as concatenated ASCII with offsets[n_barcodes + 1]; A C G T U in either case.
+ * Texts, for `window` W (1 .. MNC_DEMUX_MAX_WINDOW): the FRONT text of a read of L bases is its first min(W, L) bases, the
+ * REAR text its last min(W, L) bases read backwards and complemented -- one pattern serves both ends.  A base that is none of
+ * ACGTU (either case) matches nothing.
+ * Search: d(p, t) = the smallest edit distance (unit costs) of the whole pattern p to any substring of t: the smallest entry
+ * of the last row of the classic table with first row 0 and first column i.  e(p, t) = the first text index at which it is
+ * attained; -1 when no column is below |p|, the empty substring's distance (so an empty text gives d = |p|, e = -1).
+ * Per end: best = the barcode with the smallest d, the lower index on a tie; second = the smallest d among the OTHER
+ * barcodes.  The end HITS iff best.d <= max_dist and second.d - best.d >= min_margin (a single barcode passes the margin).
+ * Per read, by `ends`: MNC_DEMUX_FRONT -- the front hit decides, the rear is not searched; MNC_DEMUX_BOTH -- both ends must
+ * hit, with the same barcode; MNC_DEMUX_EITHER -- one hit decides, two hits with the same barcode too, two hits with
+ * different barcodes make the read a CONFLICT.
+ * Counts, additive over adds, engines and ranks: reads[n_barcodes + 2] -- per barcode, then the reads with none, then the
+ * conflicts; and for an accumulator of an index taxa[n_barcodes + 1][n_genomes][3] -- the three modes of mnc_counts (reads,
+ * whole read length, mlen) of the assigned reads, per barcode; the last row takes the reads without a barcode, conflicts
+ * among them.  taxa is filled by mnc_engine_add_demux only. */
+typedef struct mnc_demux mnc_demux;
+#define MNC_DEMUX_MAX_BARCODES 256           /* patterns in a set */
+#define MNC_DEMUX_MAX_LEN 64                 /* bases of a pattern: one word of the bit-vector search */
+#define MNC_DEMUX_MAX_WINDOW 1024            /* bases searched at an end */
+#define MNC_DEMUX_FRONT  0
+#define MNC_DEMUX_BOTH   1
+#define MNC_DEMUX_EITHER 2
+/* per read of the latest add */
+typedef struct {
+	int16_t  barcode;              /* the read's barcode; -1 none, -2 conflict */
+	uint8_t  d_front, d_rear;      /* that end's best distance, whichever barcode's; 255 where the end is not searched */
+	uint16_t cut_front, cut_rear;  /* e + 1 of the read's barcode at an end that hit with it, else 0: the bases a trimmer drops */
+} mnc_demux_tag_t;
+/* idx: the index whose genomes the taxa rows count, or NULL for an accumulator without taxa (which any engine of the device
+ * may add to).  MNC_ERR_ARG, before any device is looked at: n_barcodes outside 1 .. MNC_DEMUX_MAX_BARCODES; a pattern of no
+ * bases or more than MNC_DEMUX_MAX_LEN (the message names the barcode), a character that is none of ACGTU (the barcode and the
+ * position); window outside 1 .. MNC_DEMUX_MAX_WINDOW; max_dist < 0; min_margin < 0; an unknown `ends`; cap_reads outside
+ * 1 .. 2^31 - 1.  MNC_ERR_NODEVICE without a gfx950 device, MNC_ERR_NOMEM when 8 bytes per read and the counts do not fit the
+ * HBM that is free. */
+int  mnc_demux_create(mnc_index *idx_or_null, int device, const uint8_t *barcodes, const int64_t *bc_offsets, int32_t n_barcodes,
+                      int32_t window, int32_t max_dist, int32_t min_margin, int32_t ends, int64_t cap_reads, mnc_demux **out);
+/* frees the accumulator and the HBM it holds (waits for the work queued on it) */
+void mnc_demux_free(mnc_demux *dm);
+/* every count zero, every tag {-1, 255, 255, 0, 0} (the barcodes stay); asynchronous */
+int  mnc_demux_reset(mnc_demux *dm);
+/* HBM the accumulator holds */
+int  mnc_demux_device_bytes(const mnc_demux *dm, int64_t *bytes);
+/* word_bits: 32 when every pattern is at most 32 bases (the 32-bit kernel runs), else 64; the sums of reads[] as they stand
+ * (waits for the adds queued so far).  Any pointer may be NULL. */
+int  mnc_demux_info(mnc_demux *dm, int32_t *word_bits, int64_t *n_assigned, int64_t *n_none, int64_t *n_conflict);
+/* NOT for production callers -- a test and measurement switch, like mnc_engine_set_debug: 64 runs the 64-bit kernel whatever
+ * the patterns (the same answer, more slowly), 0 chooses by the longest again.  It may change or go in any release. */
+int  mnc_demux_set_word_bits(mnc_demux *dm, int bits);
+/* The search on the caller's own arrays -- bases, and offsets[n_reads + 1] from 0 -- host arrays, or with on_device != 0 HBM
+ * arrays that are complete (as mnc_engine_add_pileup_quals takes its qualities).  Writes tags [0, n_reads) and adds to
+ * reads[]; taxa is left alone.  Host arrays are checked (MNC_ERR_ARG: offsets not ascending from 0), copied, and free again on
+ * return; with device arrays the call is asynchronous on the accumulator's stream.  MNC_ERR_RANGE beyond cap_reads. */
+int  mnc_demux_add(mnc_demux *dm, const uint8_t *bases, const int64_t *offsets, int64_t n_reads, int on_device);
+/* The same search on the last classified batch of `eng` as it stands in HBM, then taxa from the batch's assign / best:
+ * asynchronous on the engine's stream, no host wait.  Both contracts serve (mlen is what the contract reports).
+ * MNC_ERR_ARG: another device, another index than the accumulator's own (an accumulator without one takes any), no batch
+ * classified yet; MNC_ERR_UNSUPPORTED after a call that ran both passes; MNC_ERR_RANGE beyond cap_reads.  The accumulator is
+ * untouched on any error. */
+int  mnc_engine_add_demux(mnc_engine *eng, mnc_demux *dm);
+/* tags [first, first + n) of the latest add (MNC_ERR_ARG outside cap_reads).  Waits. */
+int  mnc_demux_fetch_tags(mnc_demux *dm, int64_t first, int64_t n, mnc_demux_tag_t *out);
+/* reads[n_barcodes + 2] and taxa[n_barcodes + 1][n_genomes][3], int64; either may be NULL; taxa of an accumulator without an
+ * index: MNC_ERR_ARG.  Waits. */
+int  mnc_demux_fetch_counts(mnc_demux *dm, int64_t *reads, int64_t *taxa);
+/* The raw additive words and the tag store (device pointers; any may be NULL; d_taxa is NULL without an index), for a
+ * collective of the caller's.  Ordered behind the adds only after a read-out call or a sync of the engines that added. */
+int  mnc_demux_device(mnc_demux *dm, const int64_t **d_reads, const int64_t **d_taxa, const mnc_demux_tag_t **d_tags);
 
 /* ---------------------------------------------------------------- FASTQ batches and read routing
  * Replaces the per-record Biopython objects of the reference's loop:

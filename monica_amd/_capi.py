@@ -113,6 +113,8 @@ EXPORTS = [
     "mnc_carry_add_lists", "mnc_carry_merge", "mnc_carry_info", "mnc_carry_fetch", "mnc_carry_device",
     "mnc_lca_create", "mnc_lca_free", "mnc_lca_reset", "mnc_lca_device_bytes", "mnc_lca_info", "mnc_engine_add_lca",
     "mnc_lca_add_carry", "mnc_lca_fetch", "mnc_lca_fetch_nodes", "mnc_lca_device",
+    "mnc_demux_create", "mnc_demux_free", "mnc_demux_reset", "mnc_demux_device_bytes", "mnc_demux_info", "mnc_demux_set_word_bits",
+    "mnc_demux_add", "mnc_engine_add_demux", "mnc_demux_fetch_tags", "mnc_demux_fetch_counts", "mnc_demux_device",
 ]
 
 
@@ -335,6 +337,17 @@ def lib():
     sig("mnc_lca_fetch", i32, [vp, vp, vp])
     sig("mnc_lca_fetch_nodes", i32, [vp, i64, i64, vp])
     sig("mnc_lca_device", i32, [vp, pp, pp])
+    sig("mnc_demux_create", i32, [vp, i32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64, pp])
+    sig("mnc_demux_free", None, [vp])
+    sig("mnc_demux_reset", i32, [vp])
+    sig("mnc_demux_device_bytes", i32, [vp, C.POINTER(i64)])
+    sig("mnc_demux_info", i32, [vp, C.POINTER(C.c_int32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)])
+    sig("mnc_demux_set_word_bits", i32, [vp, i32])
+    sig("mnc_demux_add", i32, [vp, vp, vp, i64, i32])
+    sig("mnc_engine_add_demux", i32, [vp, vp])
+    sig("mnc_demux_fetch_tags", i32, [vp, i64, i64, vp])
+    sig("mnc_demux_fetch_counts", i32, [vp, vp, vp])
+    sig("mnc_demux_device", i32, [vp, pp, pp, pp])
     _LIB = L
     return L
 
@@ -721,6 +734,12 @@ class Engine:
         ancestor of its candidate genomes in the taxonomy of `lca`, and write the reads' nodes.  Asynchronous."""
         self._add("mnc_engine_add_lca", lca)
         lca.n_reads = self.n_reads
+
+    def add_demux(self, demux):
+        """`mnc_engine_add_demux`: search the barcodes of `demux` in both ends of every read of the last classified batch, as
+        it stands in HBM, write the reads' tags and count reads -- and taxa -- per barcode.  Asynchronous."""
+        self._add("mnc_engine_add_demux", demux)
+        demux.n_reads = self.n_reads
 
     def _add(self, symbol, acc, *args):
         check(getattr(lib(), symbol)(self._h, acc._h if acc is not None else None, *args))
@@ -1427,6 +1446,77 @@ class Lca(_Accumulator):
         a, b = C.c_void_p(), C.c_void_p()
         check(lib().mnc_lca_device(self._h, C.byref(a), C.byref(b)))
         return int(a.value or 0), int(b.value or 0)
+
+
+# ---------------------------------------------------------------------------------- demux
+DEMUX_MAX_BARCODES, DEMUX_MAX_LEN, DEMUX_MAX_WINDOW = 256, 64, 1024         # MNC_DEMUX_MAX_*
+DEMUX_FRONT, DEMUX_BOTH, DEMUX_EITHER = 0, 1, 2                              # MNC_DEMUX_*: which ends decide
+DEMUX_CAP_READS = 1 << 20               # reads per add when the caller names none: 8 MiB of HBM
+DEMUX_TAG_DTYPE = np.dtype([("barcode", "<i2"), ("d_front", "u1"), ("d_rear", "u1"), ("cut_front", "<u2"), ("cut_rear", "<u2")])   # mnc_demux_tag_t
+
+
+class Demux(_Accumulator):
+    """Owner of an ``mnc_demux``: the barcodes `barcodes` (str / bytes / uint8 arrays of 1 .. 64 bases) searched in the first
+    and the last `window` bases of every read within `max_dist` edits, the runner-up at least `min_margin` worse; `ends`
+    says which ends decide (include/monica_amd.h, "demux").  Reads are counted per barcode from add to add -- by `add` on
+    the caller's arrays, by `Engine.add_demux` on a classified batch, which with an `index` also counts taxa per barcode
+    -- and the tags are the latest add's.  `cap_reads`: the most reads an add may hold."""
+
+    _c = "demux"
+
+    def __init__(self, index, barcodes, window=150, max_dist=6, min_margin=2, ends=DEMUX_EITHER, cap_reads=DEMUX_CAP_READS, device=0):
+        self.index = index
+        pats = [np.frombuffer(b.encode() if isinstance(b, str) else bytes(b), dtype=np.uint8) if isinstance(b, (str, bytes, bytearray))
+                else np.ascontiguousarray(b, dtype=np.uint8) for b in barcodes]
+        self.n_barcodes = len(pats)
+        self.n_genomes = len(index.genome_names) if index is not None else 0
+        self._off = np.zeros(self.n_barcodes + 1, dtype=np.int64)
+        self._off[1:] = np.cumsum([len(p) for p in pats])
+        self._bases = np.concatenate(pats + [np.zeros(1, dtype=np.uint8)])
+        self.n_reads = 0                                        # of the latest add (add, Engine.add_demux)
+        self._create(index, device, self._bases.ctypes.data, self._off.ctypes.data, self.n_barcodes, int(window), int(max_dist), int(min_margin),
+                     int(ends), int(cap_reads))
+
+    def add(self, bases, offsets, n_reads=None, on_device=False):
+        """`mnc_demux_add`: the search on (bases uint8, offsets int64[n + 1]) -- numpy arrays, or with `on_device` two
+        device addresses and `n_reads`.  Tags and `reads`; no taxa."""
+        if not on_device:
+            bases, offsets = np.ascontiguousarray(bases, dtype=np.uint8), np.ascontiguousarray(offsets, dtype=np.int64)
+            n_reads = len(offsets) - 1
+            check(lib().mnc_demux_add(self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, n_reads, 0))
+        else:
+            check(lib().mnc_demux_add(self._h, int(bases), int(offsets), int(n_reads), 1))
+        self.n_reads = int(n_reads)
+
+    def tags(self, first=0, n=None):
+        """DEMUX_TAG_DTYPE[n]: the tags of reads [first, first + n) of the latest add (to its end by default)."""
+        n = self.n_reads - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=DEMUX_TAG_DTYPE)
+        check(lib().mnc_demux_fetch_tags(self._h, int(first), n, out.ctypes.data if out.size else None))
+        return out
+
+    def counts(self):
+        """(reads int64[n_barcodes + 2], taxa int64[n_barcodes + 1, n_genomes, 3] or None without an index)."""
+        reads = np.zeros(self.n_barcodes + 2, dtype=np.int64)
+        taxa = np.zeros((self.n_barcodes + 1, self.n_genomes, 3), dtype=np.int64) if self.index is not None else None
+        check(lib().mnc_demux_fetch_counts(self._h, reads.ctypes.data, taxa.ctypes.data if taxa is not None else None))
+        return reads, taxa
+
+    def info(self):
+        """{"word_bits", "n_assigned", "n_none", "n_conflict"} as they stand (waits for the adds queued so far)."""
+        w, v = C.c_int32(0), [C.c_int64(0) for _ in range(3)]
+        check(lib().mnc_demux_info(self._h, C.byref(w), *[C.byref(x) for x in v]))
+        return dict(zip(("word_bits", "n_assigned", "n_none", "n_conflict"), (int(w.value),) + tuple(int(x.value) for x in v)))
+
+    def set_word_bits(self, bits):
+        """`mnc_demux_set_word_bits`: 64 runs the 64-bit kernel whatever the patterns, 0 chooses by the longest."""
+        check(lib().mnc_demux_set_word_bits(self._h, int(bits)))
+
+    def device(self):
+        """(device address of reads[], of taxa[] or 0, of the tags): `mnc_demux_device`."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().mnc_demux_device(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value or 0), int(b.value or 0), int(c.value or 0)
 
 
 # ---------------------------------------------------------------------------------- host helpers

@@ -50,6 +50,21 @@ struct Accum {
 		he = hipMalloc(p, n);
 		if (he == hipSuccess) bufs.push_back(*p), bytes += (int64_t)n; else *p = nullptr;
 	}
+	// a buffer made by `alloc` that holds `cap` bytes grows to `need`: the old one is let go, its contents with it (the caller
+	// has waited for its readers).  On a failure *p is nullptr and cap 0.
+	void regrow(hipError_t &he, void **p, size_t &cap, size_t need)
+	{
+		if (need <= cap || he != hipSuccess) return;
+		const auto at = std::find(bufs.begin(), bufs.end(), *p);
+		if (*p && at != bufs.end()) {
+			bufs.erase(at);
+			(void)hipFree(*p);
+			bytes -= (int64_t)(cap ? cap : 8);
+		}
+		cap = 0;
+		alloc(he, p, need);
+		if (he == hipSuccess) cap = need;
+	}
 	void streams(hipError_t &he)
 	{
 		if (he == hipSuccess) he = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);

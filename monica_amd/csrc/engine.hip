@@ -121,6 +121,9 @@ int carry_add(mnc_carry *cc, const Batch &B, int n_contigs, int n_genomes, int64
 const Accum *as_accum(const mnc_lca *lc);                   // k_lca.hip
 int lca_fits(const mnc_lca *lc, const Batch &B);
 int lca_add(mnc_lca *lc, const Batch &B, hipStream_t st);
+const Accum *as_accum(const mnc_demux *dm);                 // k_demux.hip
+int demux_fits(const mnc_demux *dm, const Batch &B);
+int demux_add(mnc_demux *dm, const Batch &B, hipStream_t st);
 
 // ---------------------------------------------------------------- run offsets of the partition
 // The sketch writes one histogram row per tile ([tile][bucket]); the query records are laid out
@@ -1905,6 +1908,19 @@ extern "C" int mnc_engine_add_lca(mnc_engine *e, mnc_lca *lc)
 	if (int rc = lca_fits(lc, e->B)) return rc;
 	HIP_TRY(hipSetDevice(e->device));
 	return lca_add(lc, e->B, e->stream);
+}
+
+// ---------------------------------------------------------------- barcodes of the last batch
+// The reads' own ends searched for the barcodes of a set (k_demux.hip), then per barcode what mnc_count_taxa counts: the
+// common checks -- any contract serves, an accumulator without an index takes any engine of its device -- then the tag
+// store's capacity; two kernels on the engine's stream.  An empty batch is an add of no reads.
+extern "C" int mnc_engine_add_demux(mnc_engine *e, mnc_demux *dm)
+{
+	if (!e || !dm) return MNC_ERR_ARG;
+	if (int rc = add_precheck(e, as_accum(dm), "barcodes", nullptr, as_accum(dm)->idx == nullptr)) return rc;
+	if (int rc = demux_fits(dm, e->B)) return rc;
+	HIP_TRY(hipSetDevice(e->device));
+	return demux_add(dm, e->B, e->stream);
 }
 
 // ---------------------------------------------------------------- candidates of the last batch, carried across index parts

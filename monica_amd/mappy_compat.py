@@ -383,10 +383,16 @@ class Aligner:
         acc.node_names = node_names
         return acc
 
+    def demux(self, barcodes, window=150, max_dist=6, min_margin=2, ends=_capi.DEMUX_EITHER, cap_reads=_capi.DEMUX_CAP_READS):
+        """A barcode accumulator (`_capi.Demux`) for this index on this object's device: pass it to `map_batch`, then read
+        `tags()` -- which sample each read is from -- and `counts()`, the reads and the taxon table per barcode."""
+        return _capi.Demux(self._index, barcodes, window=window, max_dist=max_dist, min_margin=min_margin, ends=ends, cap_reads=cap_reads,
+                           device=self._device)
+
     def map_batch(self, bases, offsets, min_mapq=0, coverage=None, coverage_what=_capi.COV_ASSIGNED, pileup=None, pileup_what=_capi.COV_GATED,
                   abundance=None, quals=None, linkage=None, linkage_what=_capi.COV_GATED,
                   haplotag=None, haplotag_what=_capi.COV_GATED, phased=None, phased_what=_capi.COV_GATED,
-                  haplos=None, haplos_what=_capi.COV_GATED, lca=None):
+                  haplos=None, haplos_what=_capi.COV_GATED, lca=None, demux=None):
         """Classify one micro-batch.  Returns (assign, best, nhits, hit_offsets, hits) where
         hits[hit_offsets[r]:hit_offsets[r+1]] are the (rid, mapq, nm, mlen) of the hits of read r
         that pass `is_primary and mapq >= min_mapq`.  With `coverage` (an accumulator of `coverage()`), the batch is
@@ -399,7 +405,9 @@ class Aligner:
         rest or None) -- an accumulator of `haplotag()` and pileups of `pileup()` -- the batch's columns are added to the
         pileup of the haplotype their record is decided for (`Engine.add_pileup_phased`), `phased_what` one selector; with
         `haplos` (an accumulator of `haplos()`) the batch is added to it, `haplos_what` one selector; with `lca` (an
-        accumulator of `lca()`) every read is placed on its taxonomy, and its `nodes()` are this batch's."""
+        accumulator of `lca()`) every read is placed on its taxonomy, and its `nodes()` are this batch's; with `demux` (an
+        accumulator of `demux()`) every read's ends are searched for its barcodes, its `tags()` are this batch's and its
+        `counts()` grow by the batch's reads and taxa per barcode."""
         eng = self.engine()
         try:
             assign, best, nhits = eng.classify(bases, offsets, min_mapq)
@@ -424,6 +432,8 @@ class Aligner:
             eng.add_haplos(haplos, haplos_what)
         if lca is not None:
             eng.add_lca(lca)
+        if demux is not None:
+            eng.add_demux(demux)
         hit_off, hits = eng.fetch_hits()
         return assign, best, nhits, hit_off, hits
 
